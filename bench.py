@@ -59,9 +59,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# (before the HIP runtime starts: the host-fed batch runs three encoder streams + their side streams; the runtime's default
-# of 4 hardware queues makes some of them take turns.  A process-wide choice, so the benchmark makes it, not the library.)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 FILT = 0
 CONFIGS = {
@@ -457,6 +454,48 @@ def run_timed(wl, steps, warmup, barrier, dev, red_dev=None):
     return shard.max_over_ranks(elapsed, red_dev if red_dev is not None else dev), step_ms, stage_ms, calls
 
 
+DUMP_BUDGET_BYTES = 64_000_000      # all ranks' .npy files together
+DUMP_SEED = 20240611                # the byte sample of streams too large to write whole
+
+
+def dump_outputs(wl, out_dir, rank, world):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- every frame's return code, stream length
+    and stream bytes -- as .npy files (float64; the bytes float32) so that two builds can be compared output for output.  When
+    this rank's streams do not fit its share of DUMP_BUDGET_BYTES, streams.npy holds the bytes at positions drawn with DUMP_SEED
+    from their concatenation (the same positions wherever the lengths agree); stream_crc32.npy covers every byte regardless."""
+    if getattr(wl, "cross_step", False) and wl._k >= 1 and (wl._k - 1) & 1:
+        out, sizes, rcs = wl.out2, wl.sizes2, wl.rcs2                # (the last step went into the second set of buffers)
+    else:
+        out, sizes, rcs = wl.out, wl.sizes, wl.rcs
+    if hasattr(sizes, "cpu"):
+        sizes, rcs = sizes.cpu().numpy(), rcs.cpu().numpy()
+    sizes = np.asarray(sizes).astype(np.int64)
+    B, stride = out.shape
+    crcs = np.empty(B, np.float64)
+    for k in range(B):
+        row = out[k, : int(sizes[k])]
+        crcs[k] = zlib.crc32((row.cpu().numpy() if hasattr(row, "cpu") else row).tobytes())
+    total = int(sizes.sum())
+    cap = max(0, (DUMP_BUDGET_BYTES // world - 4 * 128 - 3 * 8 * B) // 4)
+    if total <= cap:
+        pos = np.arange(total, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, cap, dtype=np.int64))
+    starts = np.cumsum(sizes) - sizes
+    frame = np.searchsorted(starts, pos, side="right") - 1                # (frames with empty streams own no position)
+    flat = frame * stride + (pos - starts[frame])
+    if hasattr(out, "cpu"):
+        import torch
+        data = out.reshape(-1)[torch.from_numpy(flat).to(out.device)].cpu().numpy()
+    else:
+        data = out.reshape(-1)[flat]
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    for name, arr in (("return_codes", np.asarray(rcs).astype(np.float64)), ("stream_sizes", sizes.astype(np.float64)),
+                      ("stream_crc32", crcs), ("streams", data.astype(np.float32))):
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), arr)
+
+
 def pingpong_object(bw, name, rank, dev, local_rank, barrier, all_ranks_ok, world, red_dev=None, n=6):
     """The rank's share of a batch configuration and the NEXT share of it, coded by two encoders in turns through the
     asynchronous half of the API (icerx_encode_device_async on a stream each; the host waits for launch k - 1 after it has
@@ -824,9 +863,16 @@ def main():
     ap.add_argument("--no-one-process", action="store_true", help="skip the one_process object (icerx_compress_batch_uint16 over every visible device)")
     ap.add_argument("--batched-probe", type=int, default=8,
                     help="also report C2 throughput with this many frames per launch (secondary figure, 0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (return codes, stream lengths, CRC-32s, stream bytes) "
+                         "as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.sweep:
+        raise SystemExit("--dump-outputs needs the timed workload; --sweep times every share in turn")
     # N > 1: the whole C4 batch (256 frames, BASELINE configs[3]: what north_star says scales) split over the ranks, every frame
     # checked; the lone C2 frame per rank is a secondary object of that line.  N = 1: C2, the configuration the metric is quoted on.
     if args.config is None:
@@ -960,6 +1006,8 @@ def main():
     elapsed_max, step_ms, stage_ms, calls = run_timed(wl, args.steps, args.warmup, barrier, dev, red_dev)
     # ... and again on what the LAST timed step left in the output buffers (the timed calls run with event timing on)
     bad_after, _ = wl.verify()
+    if args.dump_outputs:
+        dump_outputs(wl, args.dump_outputs, rank, world)             # (before the parity verdict: a build that differs leaves its outputs too)
     parity_after = all_ranks_ok(not bad_after)
     if not parity_after:
         raise SystemExit(f"rank {rank}: frames {bad_after} differ from the reference golden after the timed loop; no number reported")
@@ -1065,7 +1113,8 @@ def main():
         # library then puts its encoder streams on the low priority level's queue pool, INTEGRATION.md "Hardware queues"), quiet and crowded
         if not args.no_extras and world == 1 and "C4" in batch_host and "value" in batch_host["C4"]:
             try:
-                env = dict(os.environ, GPU_MAX_HW_QUEUES="default")
+                env = dict(os.environ)
+                env.pop("GPU_MAX_HW_QUEUES", None)
                 env.pop("ICER_HIP_STREAM_PRIO", None)
                 r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "host_batch_probe.py"), "C4"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
                 o = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

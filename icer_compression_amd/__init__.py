@@ -8,6 +8,6 @@ Only what the encode hot path needs lives here:
 """
 from . import api, synth  # noqa: F401
 
-# (Importing the package does not touch the environment.  The host-fed batch wants GPU_MAX_HW_QUEUES=8 -- a process-wide
-# HIP runtime setting that has to be in place before the runtime starts: bench.py, tools/ and tests/conftest.py set it for
-# themselves, a host program does the same, INTEGRATION.md "Hardware queues".)
+# (Importing the package does not touch the environment.  The host-fed batch runs best with more hardware queues than the
+# runtime's default (GPU_MAX_HW_QUEUES, a process-wide HIP runtime setting read when the runtime starts); it is the host
+# program's choice, INTEGRATION.md "Hardware queues".)

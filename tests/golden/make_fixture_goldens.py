@@ -8,6 +8,8 @@ Writes
                                     boatcolor512_rgb (512, 512, 3) uint8 -- boatcolor.512.bmp, the R, G, B the colour flow converts
   tests/golden/fixture_golden.json  per case: the geometry and (rc, size, crc32, sha256[:16]) of the stream of the UNTOUCHED
                                     reference build (oracle/_ref) + its decoder's verdict on that stream
+  tests/golden/boat512_bmp.json     boat.512.bmp's header bytes, length and SHA-256: the file is that header and the gray plane
+                                    (B = G = R, rows bottom-up), so tests/test_reference_fixtures.py rebuilds it byte for byte
 Only pixel data is stored -- no reference source.  The cases are the reference's own invocations:
   cli_gray_<F>     icer_util compress boat.512.bmp X --grayscale -s 3 -g 10 -f <F>      (example/src/icer_util.c:123-246; quota = w*h)
   example_gray     ./compress        4 stages, filter A,  6 segments, quota  30 000      (example/src/example_encode.c)
@@ -65,11 +67,21 @@ def cases(gray, rgb):
     return out
 
 
+def bmp_container(path, gray):
+    """header, length and SHA-256 of a gray 24-bit BMP that is nothing but its header and `gray` (checked here)"""
+    raw = open(path, "rb").read()
+    off = int.from_bytes(raw[10:14], "little")
+    assert raw[off:] == np.repeat(gray[::-1], 3).tobytes()
+    return dict(header_hex=raw[:off].hex(), size=len(raw), sha256=hashlib.sha256(raw).hexdigest())
+
+
 def main():
     boat = load_bmp_rgb("/root/reference/boat.512.bmp").astype(np.uint32)
     gray = ((77 * boat[..., 0] + 150 * boat[..., 1] + 29 * boat[..., 2]) >> 8).astype(np.uint8)
     rgb = load_bmp_rgb("/root/reference/boatcolor.512.bmp")
     np.savez_compressed(os.path.join(HERE, "fixture_planes.npz"), boat512_gray=gray, boatcolor512_rgb=rgb)
+    with open(os.path.join(HERE, "boat512_bmp.json"), "w") as fh:
+        json.dump(bmp_container("/root/reference/boat.512.bmp", gray), fh, indent=1, sort_keys=True)
     ref = Reference()
     gold = {}
     for name, planes, st, f, sg, q in cases(gray, rgb):

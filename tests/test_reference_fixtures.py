@@ -1,13 +1,15 @@
 """Known answers recorded from the reference's own CLI on its own fixture:
-`icer_util compress boat.512.bmp X --grayscale -s 3 -g 10 -f {A..Q}` (quota = w*h = 262 144).  The image is read from
-/root/reference (never copied into this repository); the test is skipped where that directory does not exist."""
+`icer_util compress boat.512.bmp X --grayscale -s 3 -g 10 -f {A..Q}` (quota = w*h = 262 144).  The image file is rebuilt
+byte for byte from its committed header and pixel plane (tests/golden/boat512_bmp.json, fixture_planes.npz) and held to the
+original file's length and SHA-256."""
 import hashlib
+import json
 import os
 
 import numpy as np
 import pytest
 
-BOAT = "/root/reference/boat.512.bmp"
+GOLD_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KAT = {0: (189566, "d12559536164296e"), 1: (188996, "851229b79048d200"), 2: (190218, "b815bf03c3ff04bc"),
        3: (188910, "0d1c9032698d7d28"), 4: (190578, "cc59339cfcbe07d1"), 5: (192612, "2d7fd5067babdf76"),
        6: (190383, "cb63818012be1eec")}
@@ -30,10 +32,22 @@ def load_bmp_gray(path):
     return ((77 * r + 150 * g + 29 * b) >> 8).astype(np.uint16)
 
 
-@pytest.mark.skipif(not os.path.exists(BOAT), reason="reference fixture not mounted")
+@pytest.fixture(scope="module")
+def boat_bmp(tmp_path_factory):
+    """boat.512.bmp, rebuilt: its header, then the gray plane with B = G = R, rows bottom-up -- the reference's file exactly"""
+    with open(os.path.join(GOLD_DIR, "boat512_bmp.json")) as fh:
+        meta = json.load(fh)
+    gray = np.load(os.path.join(GOLD_DIR, "fixture_planes.npz"))["boat512_gray"]
+    raw = bytes.fromhex(meta["header_hex"]) + np.repeat(gray[::-1], 3).tobytes()
+    assert (len(raw), hashlib.sha256(raw).hexdigest()) == (meta["size"], meta["sha256"])
+    path = tmp_path_factory.mktemp("fixture") / "boat.512.bmp"
+    path.write_bytes(raw)
+    return str(path)
+
+
 @pytest.mark.parametrize("filt", sorted(KAT))
-def test_boat_512_cli_known_answers(oracle, filt):
-    img = load_bmp_gray(BOAT)
+def test_boat_512_cli_known_answers(oracle, boat_bmp, filt):
+    img = load_bmp_gray(boat_bmp)
     assert img.shape == (512, 512)
     rc, stream, _ = oracle.compress([img], 3, filt, 10, 512 * 512)
     assert rc == 0
@@ -43,9 +57,6 @@ def test_boat_512_cli_known_answers(oracle, filt):
 # ---- the fixtures' pixel planes, committed (tests/golden/fixture_planes.npz, made by tests/golden/make_fixture_goldens.py):
 # the same known answers -- and the reference's parameters of its two example programs and of the colour CLI flow -- wherever
 # the tests run, with the reference build's encoder AND decoder verdicts (tests/golden/fixture_golden.json)
-import json  # noqa: E402
-
-GOLD_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 with open(os.path.join(GOLD_DIR, "fixture_golden.json")) as _fh:
     FIXTURE_GOLDEN = json.load(_fh)
 
@@ -62,10 +73,8 @@ def fixture_planes(name):
     return [np.ascontiguousarray(p.astype(np.uint16)) for p in (y, clip(((36962 * (b - y)) >> 16) + 128), clip(((46727 * (r - y)) >> 16) + 128))]
 
 
-def test_committed_gray_plane_is_the_fixture():
-    if not os.path.exists(BOAT):
-        pytest.skip("reference fixture not mounted")
-    assert np.array_equal(load_bmp_gray(BOAT), fixture_planes("cli_gray_A")[0])
+def test_committed_gray_plane_is_the_fixture(boat_bmp):
+    assert np.array_equal(load_bmp_gray(boat_bmp), fixture_planes("cli_gray_A")[0])
 
 
 @pytest.mark.parametrize("name", sorted(FIXTURE_GOLDEN))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The host-fed batch call (icerx_compress_batch_uint16_devices, this GPU's share of C4 / C5 from page-locked memory) in a quiet
 process and in a crowded one (two torch streams that have run kernels + a live decoder), with the environment as given:
-   GPU_MAX_HW_QUEUES=4 ICER_HIP_STREAM_PRIO=0|1 python tools/host_batch_probe.py [C4|C5]     (needs a GPU)"""
+   ICER_HIP_STREAM_PRIO=0|1 python tools/host_batch_probe.py [C4|C5]     (needs a GPU)"""
 import json
 import os
 import sys
@@ -9,12 +9,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if "GPU_MAX_HW_QUEUES" in os.environ and os.environ["GPU_MAX_HW_QUEUES"] == "default":
-    del os.environ["GPU_MAX_HW_QUEUES"]
-    os.environ["ICER_BENCH_KEEP_HW_QUEUES"] = "1"
-import bench  # noqa: E402  (sets GPU_MAX_HW_QUEUES=8 unless it is set)
-if os.environ.get("ICER_BENCH_KEEP_HW_QUEUES") == "1":
-    os.environ.pop("GPU_MAX_HW_QUEUES", None)
+import bench  # noqa: E402
 
 
 def rate(hw, n):
