@@ -21,6 +21,7 @@
 
 #include "../../include/icer_hip.h"
 #include "kernels.hpp"
+#include "launch_plan.hpp"
 
 using namespace icer;
 
@@ -160,8 +161,6 @@ bool pin_thread_near_device(int physical)
 
 }  // namespace
 
-constexpr int kMaxParts = 4;             // parts of a batch in flight per call (enqueue)
-
 struct icerx_encoder {
     int device = 0;                     // physical HIP device (hipSetDevice)
     int logical_device = 0;             // what the caller named (ICER_HIP_VIRTUAL_DEVICES maps several onto one)
@@ -169,19 +168,15 @@ struct icerx_encoder {
     int channels = 1, stages = 0, filt = 0, segments = 0, max_frames = 0;
     int sample_bits = 16;               // 8: the uint8 twins (int8 storage, 7 bit planes)
     Plan plan;
+    Tuning tuning;                      // read from the environment at create (launch_plan.hpp)
     size_t slot_quota = (size_t)-1;     // quota the current slot table was built for
     unsigned bits_per_pixel = 3;        // slot bound; doubled on overflow
     bool units_uploaded = false;
-    // Which kernel codes the units.  0 (default): the eight-wave pipeline (code_units_kernel) for large quotas, the
-    // workgroup-window coder (code_units_wg_kernel: barriers only, runs of blank chunks in closed form) in progressive
-    // mode; 1 / 2: always the pipeline / always the window coder (ICER_HIP_CODER=pipe|wg, tests and measurements).
-    int coder_mode = 0;
     bool wg_once = false;               // the next enqueue uses the window coder whatever the mode (after a unit time-out)
-    int pipe_waves = 0;                 // 0: shape of the pipeline's workgroups chosen per launch; 8 / 11: pinned (ICER_HIP_PIPE_WAVES)
     int n_cus = 256;                    // compute units of the device
     uint64_t n_timeouts = 0, n_fallbacks = 0, n_slot_retries = 0;   // icerx_encoder_stats
     uint64_t n_routed_units = 0, n_routed_launches = 0;             // icerx_encoder_routing
-    bool last_routed = false;           // the last enqueue used both coders
+    LaunchPlan last_plan;               // what the last enqueue launched
 
     DevBuf<int16_t> coef, tmp;
     DevBuf<unsigned long long> sums;
@@ -194,49 +189,21 @@ struct icerx_encoder {
     DevBuf<uint8_t> sig;                // chunk tables (family_events_kernel), max_frames * plan.sig_bytes
     DevBuf<uint32_t> sig_hist;          // per frame and family: chunks by the bit plane from which they are blank, 16 entries (family_events_kernel -> route_units_kernel)
     DevBuf<uint32_t> sig_blocks;        // Plan::sig_blocks on the device
-    DevBuf<uint8_t> events;             // event bytes (events.hpp): max_frames x bit planes x plan.sig_bytes chunks x 64, allocated at the first pipeline launch
+    DevBuf<uint8_t> events;             // event bytes (events.hpp): max_frames x bit planes x plan.sig_bytes chunks x 64, allocated at create unless ICER_HIP_CODER=wg
     DevBuf<uint8_t> route;              // max_frames * units: the coder of each unit when both share a launch
     DevBuf<uint32_t> route_list, route_ctl;   // the units of the workgroup coder (frame * units + unit), [length, cursor]
-    // sub-range splitting (coder_core.hpp "Sub-ranges"): launches of at most split_frames planes cut their dense units into
-    // pieces of about split_chunks chunks, one workgroup each (ICER_HIP_SPLIT=<chunks, 0 = off>, ICER_HIP_SPLIT_FRAMES)
-    uint32_t split_chunks = 1;          // (1: chosen per geometry when the units are planned -- plan.hpp auto_split_chunks; 2 048 on the headline frame)
-    int split_frames = 1;
-    int split_hybrid_percent = 90;      // ... whose units with at least this share of blank chunks go to the small workgroup coder (ICER_HIP_SPLIT_HYBRID)
-    bool last_split = false;
-    int last_waves = 0;                 // last launch: wavefronts per pipeline workgroup (0: the workgroup coder alone)
-    uint32_t last_subs = 0;             // last launch: sub-range workgroups
-    bool lone_as_batch = false;         // ICER_HIP_LONE_AS_BATCH=1: single-frame launches with the batch build of the pipeline (measurements)
-    int split_wgs = 0;                  // staying workgroups of the small coder in a split launch (0: one per compute unit)
-    int nosplit_percent = 20;           // split launches: units with at least this share of blank chunks are not cut into sub-ranges (their words stay
-                                        // open for long stretches: the pieces would not meet; ICER_HIP_NOSPLIT)
-    int list_waves = 0;                 // wavefronts per workgroup of the list kernel: 0 = by launch (4 for a split launch, 1 for a batch), ICER_HIP_LIST_WAVES = 1 | 2 | 4
+    // sub-range splitting (coder_core.hpp "Sub-ranges"): a launch of one gray frame cuts its dense units into pieces, one workgroup each
     DevBuf<SubDesc> subs;
     DevBuf<uint32_t> sub_order, snap_valid;
     DevBuf<Snapshot> snaps;
     DevBuf<SubRecord> sub_recs;
-#ifdef ICER_EXPERIMENT_PREFIX_CACHE
-    DevBuf<uint32_t> prefix_cache;      // (experiment build only: kernels.hpp SplitLaunch::prefix_cache)
-#endif
     hipStream_t side_stream = nullptr;  // the list kernel runs beside the pipeline kernel
     bool side_stream_borrowed = false;  // ... on a stream another encoder owns (the pooled encoders of a host batch share one)
     hipEvent_t fork[kMaxParts] = {}, join[kMaxParts] = {};   // per part of a batch (enqueue): list kernel on the side stream
     hipStream_t half_stream = nullptr;  // the odd parts of a batch coded by a synchronous call (enqueue)
     hipEvent_t part_fork = nullptr, part_join = nullptr;
-    int overlap_parts = 2;              // parts a synchronous batch call is enqueued in (ICER_HIP_OVERLAP_PARTS; 1: one stream, as the asynchronous calls)
-    int last_parts = 1;
-    int wg_waves = 0;                   // 0: the window coder's instance by launch (kernels.hpp code_units_wg_kernel); 4 / 16: pinned (ICER_HIP_WG_WAVES)
-    uint32_t list_heavy_min = 64;       // listed units with at least this many chunks that are not blank are taken first (ICER_HIP_LIST_HEAVY; route_units_kernel)
-    int test_fail_frame = -1, test_fail_unit = -1, test_fail_calls = 0;   // ICER_HIP_TEST_FAIL_UNIT (test hook, enqueue_part)
-    int overlap_first = 50;             // two parts: the first part's share of the frames in percent (ICER_HIP_OVERLAP_FIRST)
     hipEvent_t coef_ready = nullptr;    // the transform of the last enqueue is complete (coef, means, frame status): recorded before the coder
     hipStream_t io_stream = nullptr, copy_stream = nullptr;   // lib_icer-shaped entry points: their encode stream, and the coefficient write-back beside the coder
-    int hybrid_percent = 95;            // units with at least this share of blank chunks go to the small workgroup coder (ICER_HIP_HYBRID; 0: none)
-    int hybrid_wgs = 2;                 // staying workgroups of the small coder per compute unit in a batch launch (ICER_HIP_HYBRID_WGS).  Round 6: two (C4 6 525 ->
-                                        // 6 664, C5 6 526 -> 6 671 Mpix/s per call; 3: the same, 4: C5 + 0.5 %, C4 - 1.8 %, 8: C5 - 5 %; profiles/r06_logs/r06t_list_grid.log) --
-                                        // a call now enqueues its frames in two parts, each with a list kernel of its own
-    bool unit_major = true;             // batches: the pipeline kernel's workgroups position-major over the frames (ICER_HIP_UNIT_MAJOR=0: frame by frame)
-    int list_grid = 0;                  // ... or their number outright in a batch launch (ICER_HIP_LIST_GRID; 0: per compute unit as above)
-    int hybrid_frames = 2;              // ... in launches of at least this many planes (frames x channels; ICER_HIP_HYBRID_FRAMES): one gray frame alone is bound by its dense units
     DevBuf<CoderTables> tables;
     // host-API staging
     DevBuf<uint16_t> in;
@@ -272,7 +239,12 @@ struct ClearList {
     uint32_t *p[kMax];
     uint32_t words[kMax];
     int n = 0;
-    void add(void *ptr, size_t bytes) { if (bytes && n < kMax) { p[n] = static_cast<uint32_t *>(ptr); words[n] = (uint32_t)(bytes / 4); n++; } }
+    bool add(void *ptr, size_t bytes)         // false: the range does not fit (whole words, at most kMax ranges of fewer than 2^32 words)
+    {
+        if (bytes && (n == kMax || bytes % 4 || bytes / 4 > UINT32_MAX)) return false;
+        if (bytes) { p[n] = static_cast<uint32_t *>(ptr); words[n] = (uint32_t)(bytes / 4); n++; }
+        return true;
+    }
 };
 __global__ void __launch_bounds__(256) clear_ranges_kernel(ClearList cl)
 {
@@ -335,18 +307,15 @@ rgb8_to_ycbcr_kernel(const uint8_t *__restrict__ rgb, uint16_t *__restrict__ pla
     }
 }
 
+LaunchShape launch_shape(const icerx_encoder *e) { return LaunchShape{e->channels, e->max_frames, e->w, e->h, e->n_cus, (uint32_t)e->plan.subs.size()}; }
+
 int upload_units(icerx_encoder *e, size_t quota, hipStream_t st)
 {
     if (e->units_uploaded && e->slot_quota == quota) return 0;
-    // (sub-ranges are planned for encoders of a few planes only: they are used in launches of at most split_frames planes, and
-    // their private slot areas and snapshots are per frame)
-    // (... and only when a split launch is possible at all: one frame of the encoder must fit split_frames planes, and the
-    // routing that goes with it must be on -- a YUV encoder would otherwise carry sub-range areas in every frame's slots that
-    // no launch ever uses)
-    const bool plan_split = e->wg_available && e->coder_mode == 0 && e->max_frames * e->channels <= 4 && e->split_frames > 0 &&
-                            e->channels <= e->split_frames && e->hybrid_percent > 0 && e->split_chunks > 0;
-    if (plan_split && e->split_chunks == 1u) e->split_chunks = auto_split_chunks(e->plan.units, e->n_cus, e->sample_bits == 8 ? kPlanes8 : kPlanes);
-    assign_slots(&e->plan, quota, e->bits_per_pixel, plan_split ? e->split_chunks : 0u);
+    uint32_t split_chunks = 0;          // (ICER_HIP_SPLIT unset: by geometry)
+    if (plans_sub_ranges(launch_shape(e), e->tuning, e->wg_available))
+        split_chunks = e->tuning.split_chunks == 1 ? auto_split_chunks(e->plan.units, e->n_cus, e->sample_bits == 8 ? kPlanes8 : kPlanes) : (uint32_t)e->tuning.split_chunks;
+    assign_slots(&e->plan, quota, e->bits_per_pixel, split_chunks);
     const size_t n = e->plan.units.size();
     if (!e->plan.subs.empty()) {
         if (e->subs.ensure(e->plan.subs.size()) || e->sub_order.ensure(e->plan.split_launch.size())) return ICER_FATAL_ERROR;
@@ -441,7 +410,7 @@ hipError_t create_part_events(icerx_encoder *e)
         if (r == hipSuccess) r = hipEventCreateWithFlags(&e->join[k], hipEventDisableTiming);
         if (r != hipSuccess) return r;
     }
-    if (e->max_frames >= 4 && e->overlap_parts > 1) {
+    if (wants_half_stream(launch_shape(e), e->tuning)) {
         hipError_t r = hipEventCreateWithFlags(&e->part_fork, hipEventDisableTiming);
         if (r == hipSuccess) r = hipEventCreateWithFlags(&e->part_join, hipEventDisableTiming);
         if (r == hipSuccess) r = hipStreamCreateWithFlags(&e->half_stream, hipStreamNonBlocking);
@@ -459,15 +428,19 @@ const char *pool_compute_level() { const char *v = getenv("ICER_HIP_COMPUTE_LEVE
 #ifndef ICER_LONE_PAD_BYTES
 #define ICER_LONE_PAD_BYTES 12288
 #endif
-constexpr int kLonePadBytes = ICER_LONE_PAD_BYTES;      // see enqueue: LDS padding of the pipeline's workgroups in a launch of one frame
+constexpr int kLonePadBytes = ICER_LONE_PAD_BYTES;      // LDS padding of the pipeline's workgroups in a split launch (launch_plan.hpp PipeKernel::Lone)
+static_assert(kUnitWavesSmall == 8 && kUnitWavesLarge == 11, "launch_plan.hpp names the pipeline's shapes by these wave counts");
 
-// enqueue the whole pipeline for the frames [f0, f0 + n_frames) of a batch on `st` (d_frames, d_out, d_sizes, d_rcs: of frame f0); every
-// per-frame buffer of the encoder is used from frame f0 on, so that parts of a batch can be in flight on different streams (enqueue).
-// `part`: which set of the per-launch resources (route list cursor, fork / join events) it takes; `timed`: it records the stage events.
-// Returns 0 or ICER_FATAL_ERROR.
-int enqueue_part(icerx_encoder *e, int f0, int part, bool timed, const uint16_t *d_frames, int n_frames, size_t quota, uint8_t *d_out, size_t out_stride,
+// enqueue the whole pipeline for part `part` of the call `lp` -- the frames [f0, f0 + n_frames) of a batch -- on `st` (d_frames,
+// d_out, d_sizes, d_rcs: of frame f0); every per-frame buffer of the encoder is used from frame f0 on, so that parts of a batch can
+// be in flight on different streams (enqueue).  `part` also names the set of per-launch resources (route list cursor, fork / join
+// events) it takes; `timed`: it records the stage events.  Returns 0 or ICER_FATAL_ERROR.
+int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, const uint16_t *d_frames, size_t quota, uint8_t *d_out, size_t out_stride,
                  unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool clear_bound)
 {
+    const PartPlan &pp = lp.part[part];
+    const int f0 = pp.f0, n_frames = pp.n_frames;
+    const bool progressive = lp.progressive, use_wg = lp.use_wg, split = pp.split, hybrid = pp.hybrid;
     const size_t W = e->w, H = e->h, plane = W * H;
     const int C = e->channels, P = n_frames * C;
     const uint32_t n_units = (uint32_t)e->plan.units.size();
@@ -484,35 +457,23 @@ int enqueue_part(icerx_encoder *e, int f0, int part, bool timed, const uint16_t 
     uint8_t *const slots = e->slots.p + (size_t)f0 * e->plan.slot_bytes;
     uint32_t *const unit_bits = e->unit_bits.p + (size_t)f0 * n_units, *const done_bytes = e->done_bytes.p + (size_t)f0 * n_units;
     uint64_t *const final_off = e->final_off.p + (size_t)f0 * n_units;
-    // which coders this launch uses (decided from the call's arguments alone: what has to be cleared follows from it)
-    // Progressive mode: with a byte quota far below the lossless size only the first part of the priority order can end
-    // up in the stream.  The units are then launched in priority order with the quota: a unit whose finished
-    // higher-priority predecessors alone already exceed it stops (at its start, or at its next check) -- see
-    // quota_already_spent.  Not used for large quotas, where the launch order is largest-first instead.
-    const bool progressive = quota < (size_t)e->w * e->h * C / 2;
-    const bool use_wg = e->wg_available && (e->wg_once || e->coder_mode == 2 || (e->coder_mode == 0 && progressive));
-    // both coders in one batch: the bit planes that are mostly runs of blank chunks go to the workgroup coder, which closes
-    // such runs in closed form; the dense ones to the pipeline (route_units_kernel)
-    // a launch of very few planes (a single frame) cannot fill the chip with whole coding units: its dense units are cut into
-    // sub-ranges, one workgroup each, and its all-but-blank ones go to the small workgroup coder as in a batch
-    const bool split = e->wg_available && !use_wg && !progressive && e->coder_mode == 0 && e->split_chunks && n_frames * C <= e->split_frames &&
-                       !e->plan.subs.empty() && e->hybrid_percent > 0;
-    e->last_split = split;
-    const bool hybrid = split || (e->wg_available && !use_wg && !progressive && e->coder_mode == 0 && e->hybrid_percent > 0 && n_frames * C >= e->hybrid_frames);
     const size_t sub_entries = e->plan.sub_entries;
     if (split && (e->snaps.ensure((size_t)e->max_frames * sub_entries * kMaxSnaps) || e->snap_valid.ensure((size_t)e->max_frames * sub_entries * kMaxSnaps) ||
                   e->sub_recs.ensure((size_t)e->max_frames * sub_entries))) return ICER_FATAL_ERROR;
     {
         ClearList cl;
-        if (f0 == 0 && n_frames == e->max_frames && clear_bound) cl.add(e->flags.p, e->flags.n * sizeof(int));       // (the whole block at once)
+        const char *bad = nullptr;
+        auto clear = [&](const char *what, void *ptr, size_t bytes) { if (!bad && !cl.add(ptr, bytes)) bad = what; };
+        if (f0 == 0 && n_frames == e->max_frames && clear_bound) clear("frame flags", e->flags.p, e->flags.n * sizeof(int));       // (the whole block at once)
         else {
-            cl.add(dwt_ovf, (size_t)P * sizeof(int)); cl.add(mean_ovf, (size_t)P * sizeof(int)); cl.add(skip, (size_t)n_frames * sizeof(int));
-            if (clear_bound) cl.add(bound_ovf, sizeof(int));
+            clear("transform flags", dwt_ovf, (size_t)P * sizeof(int)); clear("mean flags", mean_ovf, (size_t)P * sizeof(int)); clear("skip flags", skip, (size_t)n_frames * sizeof(int));
+            if (clear_bound) clear("slot bound flag", bound_ovf, sizeof(int));
         }
-        cl.add(sums, (size_t)P * sizeof(unsigned long long));
-        if (progressive) cl.add(done_bytes, (size_t)n_frames * n_units * 4);
-        if (hybrid) { cl.add(sig_hist, (size_t)n_frames * e->plan.n_families * 16 * sizeof(uint32_t)); cl.add(route_ctl, 4 * sizeof(uint32_t)); }
-        if (split) { cl.add(e->snap_valid.p, (size_t)n_frames * sub_entries * kMaxSnaps * sizeof(uint32_t)); cl.add(e->sub_recs.p, (size_t)n_frames * sub_entries * sizeof(SubRecord)); }
+        clear("LL sums", sums, (size_t)P * sizeof(unsigned long long));
+        if (progressive) clear("unit byte counts", done_bytes, (size_t)n_frames * n_units * 4);
+        if (hybrid) { clear("chunk histograms", sig_hist, (size_t)n_frames * e->plan.n_families * 16 * sizeof(uint32_t)); clear("route list cursor", route_ctl, 4 * sizeof(uint32_t)); }
+        if (split) { clear("snapshot flags", e->snap_valid.p, (size_t)n_frames * sub_entries * kMaxSnaps * sizeof(uint32_t)); clear("sub-range records", e->sub_recs.p, (size_t)n_frames * sub_entries * sizeof(SubRecord)); }
+        if (bad) { set_error("enqueue: the clear kernel cannot take the %s range (%d ranges queued)", bad, cl.n); return ICER_FATAL_ERROR; }
         launch_clears(cl, st);
     }
     if (timed && e->timing) HIP_TRY(hipEventRecord(e->ev[0], st));
@@ -540,7 +501,6 @@ int enqueue_part(icerx_encoder *e, int f0, int part, bool timed, const uint16_t 
     // table for both coders (family_events_kernel; the window coder on its own reads the coefficients itself: table only)
     const int n_planes = e->sample_bits == 8 ? kPlanes8 : kPlanes;
     const size_t ev_frame_bytes = (size_t)n_planes * e->plan.sig_bytes * 64u;
-    if (!use_wg && e->events.ensure((size_t)e->max_frames * ev_frame_bytes + 64)) return ICER_FATAL_ERROR;
     {
         hipLaunchKernelGGL(family_events_kernel, dim3((unsigned)(e->plan.sig_blocks.size() / 2), n_frames), dim3(256), 0, st,
                            reinterpret_cast<const uint16_t *>(coef), plane, (uint32_t)W, C, e->units.p, e->sig_blocks.p, skip, sig,
@@ -548,100 +508,59 @@ int enqueue_part(icerx_encoder *e, int f0, int part, bool timed, const uint16_t 
                            use_wg ? nullptr : e->events.p + (size_t)f0 * ev_frame_bytes, ev_frame_bytes, (uint32_t)n_planes);
     }
     const uint8_t *route = nullptr;
-    e->last_routed = hybrid;
     if (hybrid) {
         hipLaunchKernelGGL(route_units_kernel, dim3((unsigned)((n_units + 255) / 256), n_frames), dim3(256), 0, st, e->units.p, n_units, sig_hist, e->plan.n_families,
-                           (uint32_t)(split ? e->split_hybrid_percent : e->hybrid_percent), 16u, route_buf, route_list, route_ctl,
-                           (uint32_t)e->nosplit_percent, (uint32_t)n_frames * n_units, e->list_heavy_min);
+                           pp.route_percent, 16u, route_buf, route_list, route_ctl, kNoSplitPercent, (uint32_t)n_frames * n_units, kListHeavyMin);
         route = route_buf;
         // the workgroup coder takes its list on a second stream, beside the pipeline kernel (it is submitted first: its
         // workgroups need most of a compute unit's LDS, which they would not find once the pipeline's have spread out)
         HIP_TRY(hipEventRecord(e->fork[part], st));
         HIP_TRY(hipStreamWaitEvent(e->side_stream, e->fork[part], 0));
-        // (a split launch wants the compute units' LDS for its pipeline workgroups: fewer staying workgroups of the small coder, ICER_HIP_SPLIT_WGS)
-        // Which instance: measured (profiles/r04_logs/r04_h_list_waves.log).  A batch runs the ONE-wave instance: C4 + 4.2 %,
-        // C5 + 2.0 % -- its list is thousands of all-blank units (a first window, then closed-form runs: nothing for a second
-        // wave to do but wait at the barriers), and one resident wave of ~ 180 registers leaves the pipeline's workgroups more
-        // of the compute unit than two of 204.  The launch of a single frame wants MORE waves per listed unit (7.8 ms with one,
-        // 6.4 with two, 6.07 with FOUR, 8.7 with eight -- LDS; profiles/r04_logs/r04_zh_list_kernel_width.log): its list is led by
-        // fifty long mid-sparse chains, where every further wave's chunk of a window is progress.
-        // ICER_HIP_LIST_WAVES=1|2|4 pins one.
-        // (a lone frame: one staying workgroup per compute unit -- 128: 6.8 ms, 256: 5.9, 512: 7.25, profiles/r06_logs/r06u_lone_list_grid.log)
-        unsigned list_grid = (unsigned)(split ? (e->split_wgs ? e->split_wgs : e->n_cus) : e->n_cus * e->hybrid_wgs);
-        if (!split && e->list_grid) list_grid = (unsigned)e->list_grid;
-        const int list_waves = e->list_waves ? e->list_waves : (split ? 4 : 1);
 #define ICER_LAUNCH_LIST(I, NS)                                                                                                          \
-        hipLaunchKernelGGL((code_units_list_kernel<I>), dim3(list_grid), dim3(64 * NS::kWgWaves), sizeof(NS::Shared), e->side_stream,    \
+        hipLaunchKernelGGL((code_units_list_kernel<I>), dim3(pp.list_grid), dim3(64 * NS::kWgWaves), sizeof(NS::Shared), e->side_stream, \
                            reinterpret_cast<const uint16_t *>(coef), plane, (uint32_t)W, (uint32_t)H, C, e->units.p, n_units,     \
                            e->tables.p, means, skip, slots, e->plan.slot_bytes, unit_bits, sig,                     \
                            e->plan.sig_bytes, route_list, route_ctl, e->prof.p ? e->prof.p + kProfWgsOffset : nullptr, (uint32_t)n_frames * n_units)
-        if (list_waves == 1) ICER_LAUNCH_LIST(WgOne, wg1); else if (list_waves == 4) ICER_LAUNCH_LIST(WgFour, wg4); else ICER_LAUNCH_LIST(WgSmall, wgs);
+        if (pp.list == ListKernel::One) ICER_LAUNCH_LIST(WgOne, wg1); else if (pp.list == ListKernel::Four) ICER_LAUNCH_LIST(WgFour, wg4); else ICER_LAUNCH_LIST(WgSmall, wgs);
 #undef ICER_LAUNCH_LIST
         HIP_TRY(hipEventRecord(e->join[part], e->side_stream));
     }
     SplitLaunch sp;
     if (split) {
-        const size_t entries = sub_entries;
-        sp.subs = e->subs.p; sp.launch = e->sub_order.p; sp.n_subs = (uint32_t)e->plan.subs.size(); sp.entries = (uint32_t)entries;
+        sp.subs = e->subs.p; sp.launch = e->sub_order.p; sp.n_subs = pp.subs; sp.entries = (uint32_t)sub_entries;
         sp.snaps = e->snaps.p; sp.snap_valid = e->snap_valid.p; sp.recs = e->sub_recs.p;
-#ifdef ICER_EXPERIMENT_PREFIX_CACHE
-        if (!e->prefix_cache.p) {
-            if (e->prefix_cache.ensure((size_t)e->max_frames * entries * 36)) return ICER_FATAL_ERROR;
-            HIP_TRY(hipMemsetAsync(e->prefix_cache.p, 0, (size_t)e->max_frames * entries * 36 * sizeof(uint32_t), st));
-        }
-        sp.prefix_cache = getenv("ICER_EXPERIMENT_NO_CACHE") ? nullptr : e->prefix_cache.p;
-#endif
     }
     // TEST HOOK (ICER_HIP_TEST_FAIL_UNIT=<frame>:<unit>[:<calls>]): the pipeline kernel of the next <calls> (default 1) calls reports a time-out for
     // that unit of that frame of the batch; nothing else changes.  tests/test_gpu_recovery.py.
     uint32_t fail_inject = ~0u;
-    if (e->test_fail_calls > 0 && !use_wg && e->test_fail_frame >= f0 && e->test_fail_frame < f0 + n_frames && e->test_fail_unit < (int)n_units) {
-        fail_inject = ((uint32_t)(e->test_fail_frame - f0) << 20) | (uint32_t)e->test_fail_unit;
-        e->test_fail_calls--;
+    if (Tuning &t = e->tuning; t.fail_calls > 0 && !use_wg && t.fail_frame >= f0 && t.fail_frame < f0 + n_frames && t.fail_unit < (int)n_units) {
+        fail_inject = ((uint32_t)(t.fail_frame - f0) << 20) | (uint32_t)t.fail_unit;
+        t.fail_calls--;
     }
     if (!use_wg) {
-        // the shape of the pipeline's workgroups: one frame alone cannot fill the chip and is bound by the chain of its
-        // largest units, which the large shape (two pixel waves, golomb state wave + two workers) shortens; a batch wants
-        // the occupancy of the small one.  ICER_HIP_PIPE_WAVES=8|11 pins one (measurements).
-        // (a split launch fills the chip: the small shape's occupancy, measured 6.63 against 6.78 ms on the headline frame)
-        const bool large = e->pipe_waves ? e->pipe_waves == kUnitWavesLarge : (n_frames == 1 && !split);
-        // A launch of one frame is bound by the chains of its largest units, not by occupancy: it runs the build without the
-        // register budget, padded to the LDS footprint of the queue-depth-8 build (49 KiB; the padding is static: the
-        // `dynamic LDS' launch parameter had no effect on a kernel that declares none).  Measured on the headline frame: 37 KiB
-        // 7.5 ms, 45.6 KiB 6.8 ms, 49.5 KiB 6.7-6.8 ms (profiles/archive/r03_logs/r03_aa.log, r03_ab.log).
-        const bool lone = n_frames * C <= e->split_frames;
-        // (a batch that is not in progressive mode -- there the priority order across frames does not matter, the order within a frame does --
-        // is launched position-major over its frames: code_units_kernel; ICER_HIP_UNIT_MAJOR=0: frame by frame as before)
-        const bool unit_major = n_frames > 1 && !progressive && e->unit_major;
-        const dim3 pipe_grid = unit_major ? dim3((unsigned)((n_units + sp.n_subs) * (unsigned)n_frames), 1) : dim3(n_units + sp.n_subs, n_frames);
+        const dim3 pipe_grid = pp.position_major ? dim3((unsigned)((n_units + sp.n_subs) * (unsigned)n_frames), 1) : dim3(n_units + sp.n_subs, n_frames);
 #define ICER_LAUNCH_PIPE(NW, OCC, PAD)                                                                                                       \
         hipLaunchKernelGGL((code_units_kernel<NW, OCC, PAD>), pipe_grid, dim3(64 * NW), 0, st,                                               \
                            reinterpret_cast<const uint16_t *>(coef), plane, (uint32_t)W, (uint32_t)H, C, e->units.p,                 \
                            progressive ? nullptr : e->work_order.p, n_units, e->tables.p, means, skip, slots,                  \
                            e->plan.slot_bytes, unit_bits, e->prof.p, done_bytes, progressive ? (uint64_t)quota : 0ull, route, sp, \
-                           unit_major ? (uint32_t)n_frames : 1u, e->events.p + (size_t)f0 * ev_frame_bytes, ev_frame_bytes, sig, e->plan.sig_bytes, fail_inject)
-        e->last_waves = large ? kUnitWavesLarge : kUnitWavesSmall;
-        e->last_subs = sp.n_subs;
-        if (large) ICER_LAUNCH_PIPE(kUnitWavesLarge, 1, 0);
-        else if (lone && !e->lone_as_batch) ICER_LAUNCH_PIPE(kUnitWavesSmall, 1, kLonePadBytes);
+                           pp.position_major ? (uint32_t)n_frames : 1u, e->events.p + (size_t)f0 * ev_frame_bytes, ev_frame_bytes, sig, e->plan.sig_bytes, fail_inject)
+        if (pp.pipe == PipeKernel::Large) ICER_LAUNCH_PIPE(kUnitWavesLarge, 1, 0);
+        else if (pp.pipe == PipeKernel::Lone) ICER_LAUNCH_PIPE(kUnitWavesSmall, 1, kLonePadBytes);
         else ICER_LAUNCH_PIPE(kUnitWavesSmall, 8, 0);
 #undef ICER_LAUNCH_PIPE
         if (split)
             hipLaunchKernelGGL(splice_units_kernel, dim3(n_units, n_frames), dim3(64 * kSpliceWaves), 0, st, e->units.p, n_units, e->tables.p, means, skip, C,
                                (uint32_t)W, (uint32_t)H, slots, e->plan.slot_bytes, unit_bits, route, sp);
         if (hybrid) HIP_TRY(hipStreamWaitEvent(st, e->join[part], 0));
-    }
-    if (use_wg) e->last_waves = 0, e->last_subs = 0;
-    if (use_wg) {
-        // (which instance: kernels.hpp code_units_wg_kernel; ICER_HIP_WG_WAVES=4|16 pins one)
-        const bool four = e->wg_waves ? e->wg_waves == 4 : (progressive || n_frames * C >= 4);
+    } else {
 #define ICER_LAUNCH_WG(I, NS)                                                                                                       \
         hipLaunchKernelGGL((code_units_wg_kernel<I>), dim3(n_units, n_frames), dim3(64 * NS::kWgWaves), sizeof(NS::Shared), st,  \
                            reinterpret_cast<const uint16_t *>(coef), plane, (uint32_t)W, (uint32_t)H, C, e->units.p,              \
                            progressive ? nullptr : e->work_order.p, n_units, e->tables.p, means, skip, slots,                      \
                            e->plan.slot_bytes, unit_bits, e->prof.p, done_bytes, progressive ? (uint64_t)quota : 0ull,              \
                            sig, e->plan.sig_bytes)
-        if (four) ICER_LAUNCH_WG(WgFour, wg4); else ICER_LAUNCH_WG(WgFull, wg);
+        if (pp.window == WindowKernel::Four) ICER_LAUNCH_WG(WgFour, wg4); else ICER_LAUNCH_WG(WgFull, wg);
 #undef ICER_LAUNCH_WG
     }
     if (timed && e->timing) HIP_TRY(hipEventRecord(e->ev[3], st));
@@ -659,37 +578,30 @@ int enqueue_part(icerx_encoder *e, int f0, int part, bool timed, const uint16_t 
     return 0;
 }
 
-// One call = one batch.  A batch of several frames coded by the SYNCHRONOUS entry points is enqueued in parts on two streams -- the
-// caller's and one of the encoder's own --, so that a part's transform and event pass run beside the coder kernels of the part before
-// it and the tail of a coder kernel (its last long units, most of the chip idle) hides behind the next part's: what a caller gets from two
-// encoders and the asynchronous calls, inside one call.  Not for the asynchronous entry points (the caller overlaps
-// whole batches itself), progressive mode, or single frames.  ICER_HIP_OVERLAP_PARTS=<1..4> (1: off).
+// One call = one batch, launched as plan_launch (launch_plan.hpp) decides.  A batch of several frames coded by the SYNCHRONOUS entry
+// points is enqueued in parts on two streams -- the caller's and one of the encoder's own --, so that a part's transform and event pass
+// run beside the coder kernels of the part before it and the tail of a coder kernel (its last long units, most of the chip idle) hides
+// behind the next part's: what a caller gets from two encoders and the asynchronous calls, inside one call.  Not for
+// the asynchronous entry points (the caller overlaps whole batches itself), progressive mode, or single frames.
 int enqueue(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t quota, uint8_t *d_out, size_t out_stride,
             unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool overlap_ok)
 {
     const int C = e->channels;
     int *bound_ovf = e->flags.p + 2 * (size_t)e->max_frames * C + e->max_frames;
-    const bool progressive = quota < (size_t)e->w * e->h * C / 2;
-    int parts = 1;
-    if (overlap_ok && e->overlap_parts > 1 && e->half_stream && !progressive && e->coder_mode == 0 && !e->wg_once && n_frames >= 2 * e->overlap_parts &&
-        n_frames * C >= e->hybrid_frames)
-        parts = e->overlap_parts;
-    e->last_parts = parts;
-    if (parts == 1) return enqueue_part(e, 0, 0, true, d_frames, n_frames, quota, d_out, out_stride, d_sizes, d_rcs, st, true);
+    const CoderState cs{e->wg_available, e->wg_once, e->half_stream != nullptr};
+    const LaunchPlan &lp = e->last_plan = plan_launch(launch_shape(e), e->tuning, cs, n_frames, quota, overlap_ok);
+    if (lp.n_parts == 1) return enqueue_part(e, lp, 0, true, d_frames, quota, d_out, out_stride, d_sizes, d_rcs, st, true);
     const size_t plane = e->w * e->h;
     HIP_TRY(hipMemsetAsync(bound_ovf, 0, sizeof(int), st));             // (shared by the parts: before the second stream forks off)
     HIP_TRY(hipEventRecord(e->part_fork, st));                          // (the second stream starts behind whatever the caller's stream holds)
     HIP_TRY(hipStreamWaitEvent(e->half_stream, e->part_fork, 0));
     // (the stages of the parts overlap: the call's span is booked on the coder stage -- bench.py's roofline divides the call's bytes by it)
     if (e->timing) { HIP_TRY(hipEventRecord(e->ev[0], st)); HIP_TRY(hipEventRecord(e->ev[1], st)); HIP_TRY(hipEventRecord(e->ev[2], st)); }
-    for (int k = 0, f0 = 0; k < parts; k++) {
-        // (two parts: the first one smaller -- its transform and event pass have nothing to hide behind)
-        int n = n_frames / parts + (k < n_frames % parts ? 1 : 0);
-        if (parts == 2) { const int n0 = std::max(1, std::min(n_frames - 1, (n_frames * e->overlap_first + 50) / 100)); n = k == 0 ? n0 : n_frames - n0; }
+    for (int k = 0; k < lp.n_parts; k++) {
+        const int f0 = lp.part[k].f0;
         hipStream_t ps = (k & 1) ? e->half_stream : st;
-        if (int rc = enqueue_part(e, f0, k, false, d_frames + (size_t)f0 * C * plane, n, quota, d_out + (size_t)f0 * out_stride, out_stride,
+        if (int rc = enqueue_part(e, lp, k, false, d_frames + (size_t)f0 * C * plane, quota, d_out + (size_t)f0 * out_stride, out_stride,
                                   d_sizes + f0, d_rcs + f0, ps, false)) return rc;
-        f0 += n;
     }
     HIP_TRY(hipEventRecord(e->part_join, e->half_stream));
     HIP_TRY(hipStreamWaitEvent(st, e->part_join, 0));
@@ -743,33 +655,8 @@ int icerx_encoder_create_ex(icerx_encoder **out, int device, size_t w, size_t h,
     e->segments = segments; e->max_frames = max_frames; e->sample_bits = sample_bits;
     const int rc = build_plan(&e->plan, w, h, channels, stages, segments, sample_bits);
     if (rc != kOk) { delete e; return rc; }
-    // tuning knob: initial per-unit slot bound in bits per pixel (doubled automatically on overflow)
-    if (const char *pw = getenv("ICER_HIP_PIPE_WAVES")) { const int v = atoi(pw); if (v == kUnitWavesSmall || v == kUnitWavesLarge) e->pipe_waves = v; }
-    if (const char *cd = getenv("ICER_HIP_CODER")) e->coder_mode = !strcmp(cd, "pipe") ? 1 : !strcmp(cd, "wg") ? 2 : 0;
-    if (const char *hy = getenv("ICER_HIP_HYBRID")) { const int v = atoi(hy); if (v >= 0 && v <= 100) e->hybrid_percent = v; }
-    if (const char *hf = getenv("ICER_HIP_HYBRID_FRAMES")) { const int v = atoi(hf); if (v >= 1) e->hybrid_frames = v; }
-    if (const char *um = getenv("ICER_HIP_UNIT_MAJOR")) e->unit_major = atoi(um) != 0;
-    if (const char *lg = getenv("ICER_HIP_LIST_GRID")) { const int v = atoi(lg); if (v >= 1 && v <= 65536) e->list_grid = v; }
-    if (const char *hw = getenv("ICER_HIP_HYBRID_WGS")) { const int v = atoi(hw); if (v >= 1 && v <= 4) e->hybrid_wgs = v; }
-    if (const char *sc = getenv("ICER_HIP_SPLIT")) { const int v = atoi(sc); if (v == 0 || v >= 128) e->split_chunks = (uint32_t)v; }
-    if (const char *sh = getenv("ICER_HIP_SPLIT_HYBRID")) { const int v = atoi(sh); if (v >= 1 && v <= 101) e->split_hybrid_percent = v; }     // (101: no unit goes to the small coder)
-    if (const char *sw = getenv("ICER_HIP_LONE_AS_BATCH")) e->lone_as_batch = atoi(sw) != 0;
-    if (const char *sw = getenv("ICER_HIP_SPLIT_WGS")) { const int v = atoi(sw); if (v >= 1 && v <= 4096) e->split_wgs = v; }
-    if (const char *sf = getenv("ICER_HIP_SPLIT_FRAMES")) { const int v = atoi(sf); if (v >= 0) e->split_frames = v; }
-    if (const char *ns = getenv("ICER_HIP_NOSPLIT")) { const int v = atoi(ns); if (v >= 1 && v <= 101) e->nosplit_percent = v; }
-    if (const char *op = getenv("ICER_HIP_OVERLAP_PARTS")) { const int v = atoi(op); if (v >= 1 && v <= kMaxParts) e->overlap_parts = v; }
-    if (const char *tf = getenv("ICER_HIP_TEST_FAIL_UNIT")) {
-        int f = -1, u = -1, c = 1;
-        if (sscanf(tf, "%d:%d:%d", &f, &u, &c) >= 2 && f >= 0 && f < (1 << 11) && u >= 0 && u < (1 << 20) && c >= 1) { e->test_fail_frame = f; e->test_fail_unit = u; e->test_fail_calls = c; }
-    }
-    if (const char *ww = getenv("ICER_HIP_WG_WAVES")) { const int v = atoi(ww); if (v == 4 || v == 16) e->wg_waves = v; }
-    if (const char *lh = getenv("ICER_HIP_LIST_HEAVY")) { const long v = atol(lh); if (v >= 1) e->list_heavy_min = (uint32_t)v; }
-    if (const char *of = getenv("ICER_HIP_OVERLAP_FIRST")) { const int v = atoi(of); if (v >= 5 && v <= 95) e->overlap_first = v; }
-    if (const char *lw = getenv("ICER_HIP_LIST_WAVES")) { const int v = atoi(lw); if (v == 1 || v == 2 || v == 4) e->list_waves = v; }
-    if (const char *bpp = getenv("ICER_HIP_SLOT_BPP")) {
-        const int v = atoi(bpp);
-        if (v >= 1 && v <= 24) e->bits_per_pixel = (unsigned)v;
-    }
+    e->tuning = parse_tuning(getenv);
+    e->bits_per_pixel = (unsigned)e->tuning.slot_bpp;
 
     int count = 0;
     hipError_t he = hipGetDeviceCount(&count);
@@ -797,7 +684,7 @@ int icerx_encoder_create_ex(icerx_encoder **out, int device, size_t w, size_t h,
         return ICER_FATAL_ERROR;
     }
     // event bytes of the pipeline coder (events.hpp): one per pixel and bit plane, in chunk order
-    if (e->coder_mode != 2 && e->events.ensure((size_t)max_frames * (size_t)(sample_bits == 8 ? kPlanes8 : kPlanes) * e->plan.sig_bytes * 64u + 64)) {
+    if (e->tuning.coder != 2 && e->events.ensure((size_t)max_frames * (size_t)(sample_bits == 8 ? kPlanes8 : kPlanes) * e->plan.sig_bytes * 64u + 64)) {
         icerx_encoder_destroy(e);
         return ICER_FATAL_ERROR;
     }
@@ -814,7 +701,7 @@ int icerx_encoder_create_ex(icerx_encoder **out, int device, size_t w, size_t h,
         create_part_events(e) != hipSuccess) {
         (void)hipGetLastError();
         e->wg_available = false;
-        if (e->coder_mode == 2) { set_error("ICER_HIP_CODER=wg, but this device does not grant the workgroup coder its LDS block"); icerx_encoder_destroy(e); return ICER_FATAL_ERROR; }
+        if (e->tuning.coder == 2) { set_error("ICER_HIP_CODER=wg, but this device does not grant the workgroup coder its LDS block"); icerx_encoder_destroy(e); return ICER_FATAL_ERROR; }
         fprintf(stderr, "libicer_hip: the workgroup coder is not available on this device; the wave pipeline codes everything\n");
     }
 #ifdef ICER_PHASE_TIMERS
@@ -897,10 +784,9 @@ static int encode_begin(icerx_encoder *e, const uint16_t *d_frames, int n_frames
     if (enqueue(e, d_frames, n_frames, byte_quota, d_out, out_stride, (unsigned long long *)d_sizes, d_rcs, st, overlap_ok && flag == e->h_flag))
         return ICER_FATAL_ERROR;
     HIP_TRY(hipMemcpyAsync(flag, bound_ovf, sizeof(int), hipMemcpyDeviceToHost, st));
-    if (e->last_routed) HIP_TRY(hipMemcpyAsync(flag + 1, e->route_ctl.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    // (a batch enqueued in parts: the other parts' list lengths behind the two words every caller has -- only e->h_flag is that long)
-    for (int k = 1; k < e->last_parts; k++)
-        if (e->last_routed) HIP_TRY(hipMemcpyAsync(flag + 1 + k, e->route_ctl.p + 4 * k, sizeof(int), hipMemcpyDeviceToHost, st));
+    // the list length of each part that routed (a batch in parts: the other parts' behind the two words every caller has -- e->h_flag)
+    for (int k = 0; k < e->last_plan.n_parts; k++)
+        if (e->last_plan.part[k].hybrid) HIP_TRY(hipMemcpyAsync(flag + 1 + k, e->route_ctl.p + 4 * k, sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(done, st));
     return 0;
 }
@@ -926,10 +812,9 @@ static int encode_verdict(icerx_encoder *e, int n_frames, const int *flag)
 {
     const int ovf = flag[0];
     if (!ovf) {
-        if (e->last_routed) {
-            e->n_routed_units += (uint64_t)(uint32_t)flag[1]; e->n_routed_launches++;
-            if (flag == e->h_flag) for (int k = 1; k < e->last_parts; k++) e->n_routed_units += (uint64_t)(uint32_t)flag[1 + k];
-        }
+        bool routed = false;
+        for (int k = 0; k < e->last_plan.n_parts; k++) if (e->last_plan.part[k].hybrid) { routed = true; e->n_routed_units += (uint64_t)(uint32_t)flag[1 + k]; }
+        if (routed) e->n_routed_launches++;
         return 0;
     }
     if (ovf & 2) {
@@ -983,7 +868,7 @@ static int encode_device_impl(icerx_encoder *e, const uint16_t *d_frames, int n_
         if (!begun) {
             bool rg = false;
             const int rc = encode_begin(e, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, st, e->h_flag, e->done, regrow ? &rg : nullptr,
-                                        /* overlap_ok = */ !already_begun || e->last_parts > 1);
+                                        /* overlap_ok = */ !already_begun || e->last_plan.n_parts > 1);
             if (rc) return rc;
             if (rg) { *regrow = true; return 0; }
         }
@@ -1260,26 +1145,12 @@ int sub_batch_frames(int cnt, size_t frame_bytes)
     return sub;
 }
 
-// The sub-batches of a block of `cnt` frames, at most `sub` frames each.  Nothing overlaps the upload of the first sub-batch
-// or the download of the last one, so the block may start (and, with ramp = 2, end) with smaller ones: 1, 2, 4, ... frames
-// up to `sub` (ICER_HIP_BATCH_RAMP=0: all of `sub` frames -- the default, see below --, 1: rising at the start, 2: and falling
-// at the end).
+// The sub-batches of a block of `cnt` frames: `sub` frames each, the last one what is left (a block that started or ended with
+// smaller sub-batches was measured: C5 the same, C4 9 % slower, profiles/r04_logs/r04_a_host_batch_ramp.log)
 void sub_batch_plan(int cnt, int sub, std::vector<int> *first, std::vector<int> *count)
 {
-    int ramp = 0;                           // (measured, profiles/r04_logs/r04_a_host_batch_ramp.log: C5 the same with 0 / 1 / 2, C4 9 % slower with a ramp)
-    if (const char *rv = getenv("ICER_HIP_BATCH_RAMP")) { const int v = atoi(rv); if (v >= 0 && v <= 2) ramp = v; }
-    std::vector<int> head, tail;
-    int left = cnt;
-    if (ramp >= 1 && sub >= 2 && cnt >= 2 * sub)
-        for (int n = 1; n < sub && left > sub; n *= 2) { head.push_back(n); left -= n; }
-    if (ramp >= 2 && sub >= 2 && left >= 2 * sub)
-        for (int n = 1; n < sub && left > sub; n *= 2) { tail.push_back(n); left -= n; }
-    std::vector<int> sizes(head);
-    while (left > 0) { const int n = left < sub ? left : sub; sizes.push_back(n); left -= n; }
-    for (size_t i = tail.size(); i-- > 0;) sizes.push_back(tail[i]);
     first->clear(); count->clear();
-    int at = 0;
-    for (int n : sizes) { first->push_back(at); count->push_back(n); at += n; }
+    for (int at = 0; at < cnt; at += sub) { first->push_back(at); count->push_back(std::min(sub, cnt - at)); }
 }
 
 int batch_rebuild(BatchDevice *b, size_t w, size_t h, int channels, int stages, int filt, int segments, int sub, int sets)
@@ -1563,7 +1434,7 @@ int icerx_process_stats(uint64_t out[4])
 int icerx_encoder_stats(icerx_encoder *e, uint64_t out[4])
 {
     if (!e || !out) return ICER_INVALID_INPUT;
-    out[0] = e->n_timeouts; out[1] = e->n_fallbacks; out[2] = e->n_slot_retries; out[3] = (uint64_t)e->coder_mode;
+    out[0] = e->n_timeouts; out[1] = e->n_fallbacks; out[2] = e->n_slot_retries; out[3] = (uint64_t)e->tuning.coder;
     return 0;
 }
 
@@ -1577,11 +1448,15 @@ int icerx_encoder_routing(icerx_encoder *e, uint64_t out[2])
 int icerx_encoder_launch_info(icerx_encoder *e, uint32_t out[4])
 {
     if (!e || !out) return ICER_INVALID_INPUT;
-    out[0] = e->last_split ? 1u : 0u; out[1] = e->last_subs; out[2] = (uint32_t)e->last_waves; out[3] = e->last_routed ? 1u : 0u;
+    // (the last call: split if a part split, the sub-range workgroups of all parts, routed if a part routed)
+    const LaunchPlan &lp = e->last_plan;
+    out[0] = out[1] = out[3] = 0;
+    for (int k = 0; k < lp.n_parts; k++) { out[0] |= lp.part[k].split; out[1] += lp.part[k].subs; out[3] |= lp.part[k].hybrid; }
+    out[2] = lp.use_wg ? 0u : lp.part[lp.n_parts - 1].pipe == PipeKernel::Large ? (uint32_t)kUnitWavesLarge : (uint32_t)kUnitWavesSmall;
     return 0;
 }
 
-int icerx_encoder_parts(icerx_encoder *e) { return e ? e->last_parts : ICER_INVALID_INPUT; }
+int icerx_encoder_parts(icerx_encoder *e) { return e ? e->last_plan.n_parts : ICER_INVALID_INPUT; }
 
 int icerx_info(icerx_encoder *e, uint32_t *units_per_frame, uint32_t *slot_bits_per_pixel, uint64_t *slot_bytes_per_frame)
 {

@@ -418,15 +418,13 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
         //   wave per plane   4: 220   8: 437   16: 525-586   32: 537   64: 519
         //   lane per plane   4: 107            16: 435       32: 922   64: 885-921   128: 1036
         // -- the cross-over lies near 20 streams = 12 chains per compute unit (24 streams by this rule: 686).  ICER_DEC_WAVE=2
-        // pins the wave-per-plane kernel, ICER_DEC_PLANES_PER_CU moves the cross-over.
+        // pins the wave-per-plane kernel.
         const char *mode = getenv("ICER_DEC_WAVE");
         size_t n_eligible = 0;
         for (const ChainDesc &c : chains) n_eligible += c.fast ? 1u : 0u;
         const bool by_load = !mode || !mode[0];
-        size_t per_cu = 12u;
-        if (const char *pc = getenv("ICER_DEC_PLANES_PER_CU")) { const long v = atol(pc); if (v >= 1 && v <= 1000000) per_cu = (size_t)v; }
         const bool want_planes = !(mode && (mode[0] == '0' || mode[0] == '1')) && d->tables.lut_ok != 0u &&
-                                 (!by_load || n_eligible <= per_cu * (size_t)d->n_cus);
+                                 (!by_load || n_eligible <= 12u * (size_t)d->n_cus);
         size_t planes_lds = 0;
 #ifdef ICER_HOST_MOCK
         const size_t planes_lds_limit = (size_t)1 << 20;
@@ -483,14 +481,9 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
         // Longest chains first within either kernel's share (a chain's time goes with its samples): the level-1 chains of
         // every stream start at once, one or two per compute unit, and the short ones fill the gaps -- in stream order the
         // long chains of the later streams of a batch started when those of the first were half-way.
-        {
-            const char *ord = getenv("ICER_DEC_ORDER");
-            if (!(ord && ord[0] == '0')) {
-                auto longer = [](const ChainDesc &a, const ChainDesc &b) { return (uint32_t)a.w * a.h > (uint32_t)b.w * b.h; };
-                std::stable_sort(chains.begin(), chains.begin() + n_fast, longer);
-                std::stable_sort(chains.begin() + n_fast, chains.end(), longer);
-            }
-        }
+        auto longer = [](const ChainDesc &a, const ChainDesc &b) { return (uint32_t)a.w * a.h > (uint32_t)b.w * b.h; };
+        std::stable_sort(chains.begin(), chains.begin() + n_fast, longer);
+        std::stable_sort(chains.begin() + n_fast, chains.end(), longer);
         // The lane-per-plane kernel's share by size class of row ring (a launch reserves the LDS of its widest chain for every
         // workgroup, and LDS is what bounds the chains a compute unit holds: 7 of the headline stream's level-1 chains, but 14
         // of level 2 and 28 of level 3): class k = rings of at most limit >> k bytes, widest class first, each class a launch

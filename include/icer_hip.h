@@ -180,8 +180,7 @@ int icerx_encode_host(icerx_encoder *enc, const uint16_t *frames, int n_frames, 
  * _devices variant names them (one process per GPU: pass that process's device).  sizes / rcs per frame equal a
  * per-frame call of icer_compress_image_[yuv_]uint16 (reference: icer.h:440-444).  Returns 0, or the first failing
  * device's error code (icerx_last_error lists every failing device).
- * Env: ICER_HIP_BATCH_SUB=<frames per sub-batch>, ICER_HIP_BATCH_RAMP=<0|1|2> (smaller sub-batches at the start / and the
- * end of a block; 0 = off is the default), ICER_HIP_NUMA=0 (do not pin the per-device host threads to their GPU's NUMA node).
+ * Env: ICER_HIP_BATCH_SUB=<frames per sub-batch>, ICER_HIP_NUMA=0 (do not pin the per-device host threads to their GPU's NUMA node).
  * The pipeline keeps six streams per device busy.  With GPU_MAX_HW_QUEUES=8 exported before the process initialises HIP they
  * are plain streams (0.94 x the device-resident rate); with fewer hardware queues the encoders' streams are created at the low
  * priority level -- a queue pool of their own: the same 0.94 x whatever else the process has alive, and the program's own kernels
