@@ -364,3 +364,77 @@ def pin_host(arr) -> bool:
 
 def unpin_host(arr) -> None:
     load_library().icerx_unpin_host(arr.ctypes.data)
+
+
+# ---- standalone wavelet transform (include/icer_hip.h; the inverse twins are in decoder.py) --------------------------
+_WL_KINDS = ("stages", "2d", "1d")
+
+
+def _wavelet_host(lib, inverse: bool, data: np.ndarray, filt: int, stages: int, kind: str, image_w, image_h, rowstride, N, stride) -> int:
+    if kind not in _WL_KINDS:
+        raise ValueError(f"kind must be one of {_WL_KINDS}")
+    if data.dtype not in (np.uint16, np.uint8) or not data.flags["C_CONTIGUOUS"]:
+        raise ValueError("data must be a C-contiguous uint16 or uint8 array (changed in place)")
+    bits = 16 if data.dtype == np.uint16 else 8
+    pre = ("icer_inverse_wavelet_transform_" if inverse else "icer_wavelet_transform_") + kind + ("_uint16" if bits == 16 else "_uint8")
+    fn = getattr(lib, pre)
+    fn.restype = C.c_int
+    ptr = C.c_void_p(data.ctypes.data)
+    if kind == "1d":
+        N = data.size if N is None else int(N)
+        if N >= 1 and (N - 1) * stride + 1 > data.size:
+            raise ValueError("N samples at `stride` run past the array")
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
+        return fn(ptr, N, stride, filt)
+    h, w = data.shape[-2:] if data.ndim >= 2 else (1, data.size)
+    image_w = w if image_w is None else int(image_w)
+    image_h = h if image_h is None else int(image_h)
+    if kind == "stages":
+        if image_w * image_h > data.size:
+            raise ValueError("image_w * image_h runs past the array")
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint8, C.c_int]
+        return fn(ptr, image_w, image_h, stages, filt)
+    rowstride = w if rowstride is None else int(rowstride)
+    if image_h >= 1 and image_w >= 1 and (image_h - 1) * rowstride + image_w > data.size:
+        raise ValueError("the image_w x image_h region at `rowstride` runs past the array")
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    return fn(ptr, image_w, image_h, rowstride, filt)
+
+
+def wavelet_transform(data: np.ndarray, filt: int, stages: int = 1, kind: str = "stages", image_w=None, image_h=None,
+                      rowstride=None, N=None, stride: int = 1) -> int:
+    """icer_wavelet_transform_{stages,2d,1d}_{uint16,uint8} on a host array, in place (the dtype picks the twin):
+    kind "stages" (image_w x image_h, default the array's shape), "2d" (one level on an image_w x image_h region of rows
+    `rowstride` apart) or "1d" (N samples `stride` apart).  Returns the reference's icer_status."""
+    return _wavelet_host(load_library(), False, data, filt, stages, kind, image_w, image_h, rowstride, N, stride)
+
+
+def _wavelet_torch(fn, planes, stages: int, filt: int):
+    import torch
+    if not planes.is_cuda or not planes.is_contiguous() or planes.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16), torch.int8, torch.uint8):
+        raise ValueError("planes must be a contiguous cuda tensor of int16/uint16 (or int8/uint8 for the uint8 twins)")
+    if planes.dim() < 2 or planes.shape[-1] == 0 or planes.shape[-2] == 0 or planes.numel() == 0:
+        raise ValueError("planes must be a non-empty tensor (..., h, w)")
+    bits = 16 if planes.element_size() == 2 else 8
+    h, w = planes.shape[-2:]
+    n = planes.numel() // (h * w)
+    lib = load_library()
+    lib.icerx_wavelet_workspace_bytes.restype = C.c_size_t
+    lib.icerx_wavelet_workspace_bytes.argtypes = [C.c_size_t, C.c_size_t, C.c_int, C.c_int]
+    ws = torch.empty(int(lib.icerx_wavelet_workspace_bytes(w, h, n, bits)), dtype=torch.uint8, device=planes.device)
+    rcs = torch.zeros(n, dtype=torch.int32, device=planes.device)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    with torch.cuda.device(planes.device):
+        st = torch.cuda.current_stream(planes.device).cuda_stream
+        rc = fn(planes.data_ptr(), n, w, h, w * h, stages, filt, bits, ws.data_ptr(), rcs.data_ptr(), st)
+    if rc:
+        raise IcerHipError(f"wavelet transform rc={rc}")
+    return rcs
+
+
+def wavelet_forward_torch(planes, stages: int, filt: int):
+    """icerx_wavelet_forward_device on a cuda tensor (..., h, w) in place, on torch's current stream, with no host
+    synchronisation; returns the per-plane icer_status as a cuda int32 tensor.  ICER_TOO_MANY_STAGES /
+    ICER_INVALID_INPUT raise IcerHipError before anything runs."""
+    return _wavelet_torch(load_library().icerx_wavelet_forward_device, planes, stages, filt)

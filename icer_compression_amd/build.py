@@ -9,7 +9,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libicer_hip.so")
-SOURCES = ["api.hip"]
+SOURCES = ["api.hip", "wavelet_fwd.hip"]
 INCLUDE = os.path.join(PKG, "..", "include")
 
 
@@ -75,16 +75,17 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 
 DEC_LIB = os.path.join(PKG, "libicer_hip_dec.so")
+DEC_SOURCES = ["decoder.hip", "wavelet_inv.hip"]
 
 
 def build_decoder_library(force: bool = False, verbose: bool = False) -> str:
     """libicer_hip_dec.so: the decoder, a separate library -- see include/icer_hip_dec.h."""
-    deps = _deps("decoder.hip")
+    deps = [d for s in DEC_SOURCES for d in _deps(s)]
     if not force and os.path.exists(DEC_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(DEC_LIB) for d in deps):
         return DEC_LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-shared", "-fPIC", "-Wall", "-o", DEC_LIB,
-           os.path.join(CSRC, "decoder.hip")]
+    cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-shared", "-fPIC", "-Wall", "-o", DEC_LIB] + \
+        [os.path.join(CSRC, s) for s in DEC_SOURCES]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

@@ -130,3 +130,19 @@ class Decoder:
         rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
         rc = self.lib.icerx_decode_device(self.handle, n, d_data, offs, ln, d_out, frame_stride, rcs, ws, hs)
         return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+
+
+# ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------
+def inverse_wavelet_transform(data: np.ndarray, filt: int, stages: int = 1, kind: str = "stages", image_w=None, image_h=None,
+                              rowstride=None, N=None, stride: int = 1) -> int:
+    """icer_inverse_wavelet_transform_{stages,2d,1d}_{uint16,uint8} on a host array, in place; arguments as
+    api.wavelet_transform.  Returns the reference's icer_status."""
+    from . import api
+    return api._wavelet_host(load_library(), True, data, filt, stages, kind, image_w, image_h, rowstride, N, stride)
+
+
+def wavelet_inverse_torch(planes, stages: int, filt: int):
+    """icerx_wavelet_inverse_device on a cuda tensor (..., h, w) in place, on torch's current stream; returns the
+    per-plane icer_status as a cuda int32 tensor (see api.wavelet_forward_torch)."""
+    from . import api
+    return api._wavelet_torch(load_library().icerx_wavelet_inverse_device, planes, stages, filt)

@@ -247,6 +247,43 @@ int icerx_encoder_parts(icerx_encoder *enc);
 /* out[0..2] summed over all encoders of the process, including the one behind the lib_icer-shaped entry points */
 int icerx_process_stats(uint64_t out[4]);
 
+/* ---- Standalone wavelet transform, forward (lib_icer/inc/icer.h:392-395, :446-449, :434-435) ----------------------
+ * Same names, signatures, return codes and in-place effects as lib_icer (icer_wavelet.c): the caller's buffer and the
+ * return code after a call equal the reference's, ICER_INTEGER_OVERFLOW included (the transform keeps going and stores
+ * wrapped int16 / int8 values, as the reference does), and the uint8 twins work on int8 storage with int8 limits.
+ *   _stages   image_w x image_h, contiguous; ICER_TOO_MANY_STAGES (buffer untouched) when the smallest LL would have a
+ *             side below 3; no ICER_MAX_DECOMP_STAGES cap.
+ *   _2d       one level on image_w x image_h samples of a plane with `rowstride`; samples beyond image_w stay untouched.
+ *   _1d       N samples `stride` apart; only those are read or written.  Gathered and scattered with a 2-D copy: this
+ *             call exists for completeness, not speed.
+ * A line shorter than 2 samples (image_w, image_h or N < 2) returns ICER_INVALID_INPUT with the data untouched (the
+ * reference loops through SIZE_MAX there).  The transform runs on the GPU (device ICER_HIP_DEVICE, default 0); the calls
+ * are serialised like the other lib_icer-shaped entry points.
+ * icer_to_sign_magnitude_int16 / _int8 are host-only bit manipulation on caller memory.
+ * Not provided (in-place shuffles only lib_icer itself calls, or functions on lib_icer's internal context structs):
+ * interleave / deinterleave / reverse / remove_negative, the partition, bitplane, entropy-coder and packet functions,
+ * and the dimension helpers. */
+int icer_wavelet_transform_stages_uint16(uint16_t *image, size_t image_w, size_t image_h, uint8_t stages, enum icer_filter_types filt);
+int icer_wavelet_transform_2d_uint16(uint16_t *image, size_t image_w, size_t image_h, size_t rowstride, enum icer_filter_types filt);
+int icer_wavelet_transform_1d_uint16(uint16_t *data, size_t N, size_t stride, enum icer_filter_types filt);
+int icer_wavelet_transform_stages_uint8(uint8_t *image, size_t image_w, size_t image_h, uint8_t stages, enum icer_filter_types filt);
+int icer_wavelet_transform_2d_uint8(uint8_t *image, size_t image_w, size_t image_h, size_t rowstride, enum icer_filter_types filt);
+int icer_wavelet_transform_1d_uint8(uint8_t *data, size_t N, size_t stride, enum icer_filter_types filt);
+void icer_to_sign_magnitude_int16(uint16_t *data, size_t len);
+void icer_to_sign_magnitude_int8(uint8_t *data, size_t len);
+
+/* Device-resident batch transform (the path the calls above wrap).  d_planes: n_planes planes of w*h samples (row stride
+ * w; uint16 for sample_bits 16, int8 bytes for 8), plane k at d_planes + k*plane_stride samples, transformed in place
+ * with `stages` levels of filter `filt`.  Everything is enqueued on `stream` (a hipStream_t; 0 = the null stream) with no
+ * host synchronisation; d_rcs[k] (device memory) receives ICER_RESULT_OK or ICER_INTEGER_OVERFLOW for plane k on the
+ * stream.  The call itself returns ICER_TOO_MANY_STAGES / ICER_INVALID_INPUT (also for n_planes above 65535) before enqueuing anything, or
+ * ICER_FATAL_ERROR on a HIP failure.  d_workspace: icerx_wavelet_workspace_bytes(w, h, n_planes, sample_bits) bytes of
+ * device memory owned by the caller, not used by another call until this one has completed on the stream.  The inverse,
+ * icerx_wavelet_inverse_device, is in libicer_hip_dec.so. */
+size_t icerx_wavelet_workspace_bytes(size_t w, size_t h, int n_planes, int sample_bits);
+int icerx_wavelet_forward_device(void *d_planes, int n_planes, size_t w, size_t h, size_t plane_stride, int stages, int filt,
+                                 int sample_bits, void *d_workspace, int32_t *d_rcs, void *stream);
+
 const char *icerx_last_error(void);
 
 #ifdef __cplusplus

@@ -82,6 +82,27 @@ int icerx_decode_device(icerx_decoder *dec, int n, const void *d_data, const siz
 /* last error message of this thread's most recent failing call ("" if none) */
 const char *icerx_decoder_last_error(void);
 
+/* ---- Standalone wavelet transform, inverse (lib_icer/inc/icer.h:414-417, :468-471, :487-488) ----------------------
+ * The twins of the forward calls in icer_hip.h, with the same contract: buffer and return code equal the reference's
+ * (ICER_INTEGER_OVERFLOW included: wrapped values are stored and the transform goes on; the uint8 twins keep the
+ * reference's scrambled interleave of odd-length lines), ICER_TOO_MANY_STAGES leaves the buffer untouched, a line
+ * shorter than 2 samples returns ICER_INVALID_INPUT untouched, _2d leaves samples beyond image_w of each row alone, _1d
+ * touches only its N samples (gathered with a 2-D copy: for completeness, not speed).  Runs on the GPU; serialised.
+ * icer_from_sign_magnitude_int16 / _int8 are host-only.  Not provided: see icer_hip.h. */
+int icer_inverse_wavelet_transform_stages_uint16(uint16_t *image, size_t image_w, size_t image_h, uint8_t stages, enum icer_filter_types filt);
+int icer_inverse_wavelet_transform_2d_uint16(uint16_t *image, size_t image_w, size_t image_h, size_t rowstride, enum icer_filter_types filt);
+int icer_inverse_wavelet_transform_1d_uint16(uint16_t *data, size_t N, size_t stride, enum icer_filter_types filt);
+int icer_inverse_wavelet_transform_stages_uint8(uint8_t *image, size_t image_w, size_t image_h, uint8_t stages, enum icer_filter_types filt);
+int icer_inverse_wavelet_transform_2d_uint8(uint8_t *image, size_t image_w, size_t image_h, size_t rowstride, enum icer_filter_types filt);
+int icer_inverse_wavelet_transform_1d_uint8(uint8_t *data, size_t N, size_t stride, enum icer_filter_types filt);
+void icer_from_sign_magnitude_int16(uint16_t *data, size_t len);
+void icer_from_sign_magnitude_int8(uint8_t *data, size_t len);
+
+/* The inverse of icerx_wavelet_forward_device (icer_hip.h), same arguments and contract; the workspace size is
+ * icerx_wavelet_workspace_bytes of libicer_hip.so. */
+int icerx_wavelet_inverse_device(void *d_planes, int n_planes, size_t w, size_t h, size_t plane_stride, int stages, int filt,
+                                 int sample_bits, void *d_workspace, int32_t *d_rcs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
