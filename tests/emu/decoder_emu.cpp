@@ -114,6 +114,9 @@ extern "C" int emu_decoder_lut_ok(void)
 }
 extern "C" void emu_decoder_stats(unsigned long long *out) { for (int i = 0; i < 4; i++) out[i] = g_stats[i]; }
 // the wave-per-plane kernel's zero runs since the process started: [runs taken, decisions they stood for]
+// dynamic LDS that decode_chains_planes_kernel takes for a chain `w` samples wide (tests/decoder_batch_cases.py)
+extern "C" size_t emu_pw_lds_bytes(uint32_t w, int planes) { return pw_lds_bytes(w, planes); }
+
 extern "C" void emu_decoder_run_stats(unsigned long long *out) { out[0] = icer::g_pw_run_stats[0]; out[1] = icer::g_pw_run_stats[1]; }
 
 // planes[c]: >= bufsize uint16 words; for sample_bits = 8 the low byte of each word is the uint8 result.

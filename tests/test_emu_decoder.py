@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle.binding import Oracle
+from tests import decoder_batch_cases as dbc
 from tests.test_oracle_decoder import packets, random_case
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -316,3 +317,94 @@ def test_host_pipeline_on_a_mock_hip_runtime(orc, tmp_path):
             os.environ.pop("ICER_DEC_WAVE", None)
         else:
             os.environ["ICER_DEC_WAVE"] = old
+
+
+# ---- the batch cases of tests/test_gpu_decoder_batch.py, scaled down, on the mock-runtime build of decoder.hip ----------
+@pytest.fixture(scope="module")
+def mock_lib(tmp_path_factory):
+    from icer_compression_amd import decoder
+    lib_path = str(tmp_path_factory.mktemp("mock") / "libdecoder_mock.so")
+    subprocess.check_call(["g++", "-x", "c++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas",
+                           "-DICER_HOST_MOCK", "-DICER_WAVE_EMU", "-include", os.path.join(HERE, "emu", "hip_mock.h"),
+                           "-o", lib_path, os.path.join(os.path.dirname(HERE), "icer_compression_amd", "csrc", "decoder.hip")])
+    return decoder.bind(lib_path)
+
+
+@pytest.fixture(params=[None, "0", "1", "2"], ids=["by-load", "thread-per-chain", "wave-per-chain", "wave-per-plane"])
+def dec_wave(request):
+    """ICER_DEC_WAVE unset (the kernel chosen by load) or pinned"""
+    old = os.environ.get("ICER_DEC_WAVE")
+    if request.param is None:
+        os.environ.pop("ICER_DEC_WAVE", None)
+    else:
+        os.environ["ICER_DEC_WAVE"] = request.param
+    yield request.param
+    if old is None:
+        os.environ.pop("ICER_DEC_WAVE", None)
+    else:
+        os.environ["ICER_DEC_WAVE"] = old
+
+
+def _host(a):
+    """the mock's device memory is host memory"""
+    return a.ctypes.data, a
+
+
+def _mock_decoder(lib, b):
+    from icer_compression_amd import decoder
+    return decoder.Decoder(b.channels, b.stages, b.filt, b.segments, bits=b.bits, lib=lib)
+
+
+_MOCK_BATCHES = {}
+
+
+def _mock_batch(orc, ch, bits, filt):
+    key = (ch, bits, filt)
+    if key not in _MOCK_BATCHES:
+        _MOCK_BATCHES[key] = dbc.mixed_batch(orc, ch, bits, filt, "mock")
+    return _MOCK_BATCHES[key]
+
+
+@pytest.mark.parametrize("filt", range(7))
+def test_mock_batch_filters_channels_bits(mock_lib, orc, dec_wave, filt):
+    """cases 1 + 2: gray and YUV, 16 and 8 bits, three sizes (two of one width) each at non-adjacent positions, lossless
+    and quota-cut streams, and streams that stop early in between; host and "device" buffers"""
+    for ch in (1, 3):
+        for bits in (16, 8):
+            b = _mock_batch(orc, ch, bits, filt)
+            d = _mock_decoder(mock_lib, b)
+            label = f"filt {filt} ch {ch} bits {bits} mode {dec_wave}"
+            dbc.decode_host(d, b, label)
+            dbc.decode_device(d, b, _host, lambda a: a, label)
+            d.close()
+
+
+def test_mock_second_header_pass(mock_lib, orc, dec_wave):
+    """case 5: more packets than count_headers_kernel's first capacity"""
+    b = dbc.header_pass_batch(orc)
+    d = _mock_decoder(mock_lib, b)
+    dbc.decode_host(d, b, f"mode {dec_wave}")
+    dbc.decode_device(d, b, _host, lambda a: a, f"mode {dec_wave}")
+    d.close()
+
+
+@pytest.mark.parametrize("bits", [16, 8])
+def test_mock_decoder_reused_across_calls(mock_lib, orc, bits):
+    """case 6: one decoder object, a large call, a smaller different one, the large one again"""
+    large, small = dbc.reuse_batches(orc, bits, "mock")
+    d = _mock_decoder(mock_lib, large)
+    for k, b in enumerate((large, small, large, small)):
+        dbc.decode_device(d, b, _host, lambda a: a, f"call {k}")
+        dbc.decode_host(d, b, f"call {k}")
+    d.close()
+
+
+@pytest.mark.parametrize("ch,bits", [(1, 16), (3, 8)])
+def test_mock_blob_layout(mock_lib, orc, ch, bits):
+    """case 7: junk around and between the streams, offsets out of order, the same bytes twice, a zero-length entry inside
+    another stream; ws / hs in-values kept only where a stream holds no valid packet"""
+    layout = dbc.Layout(orc, _mock_batch(orc, ch, bits, 4))
+    d = _mock_decoder(mock_lib, layout.batch)
+    for device in (True, False):
+        dbc.layout_call(d, layout, device, _host, lambda a: a, f"device={device}")
+    d.close()
