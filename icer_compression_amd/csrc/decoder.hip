@@ -5,11 +5,14 @@
 //   chains of all streams (one wavefront per chain; one thread per chain with ICER_DEC_WAVE=0) | sign-magnitude
 //   removal + LL mean | inverse DWT, one level at a time, one thread per line, all frames of a geometry per launch
 //   | clamp, narrow, copy back.
+// icerx_decode_device_async runs the same chain kernels with everything planned on the device (decoder_async.hpp).
 // First version: correctness before speed (HISTORY.md 6b (summary: DESIGN.md 8)); every loop is bounded by the stream / image size and no
 // kernel waits on another thread.
 #ifdef ICER_HOST_MOCK
 #define ICER_LAUNCH_PLANES(kernel, grid, shmem, ...) ICER_LAUNCH_WAVE(kernel, grid, shmem, __VA_ARGS__)
 #define ICER_LAUNCH_WAVE_ON(stream, kernel, grid, shmem, ...) ICER_LAUNCH_WAVE(kernel, grid, shmem, __VA_ARGS__)
+#define ICER_LAUNCH_ON(stream, kernel, grid, block, shmem, ...) ICER_LAUNCH(kernel, grid, block, shmem, __VA_ARGS__)
+#define ICER_LAUNCH_PLANES_ON(stream, kernel, grid, shmem, ...) ICER_LAUNCH_PLANES(kernel, grid, shmem, __VA_ARGS__)
 #else
 #include <hip/hip_runtime.h>
 // kernel launches go through these two macros so that tests/emu/hip_mock.h (CPU, tests only) can stand in for them
@@ -18,6 +21,8 @@
 // (a workgroup of one wavefront per bit plane; the CPU mock runs the waves of a workgroup in turns inside one call)
 #define ICER_LAUNCH_PLANES(kernel, grid, shmem, ...) kernel<<<(grid), 64 * kPwWaves, (shmem)>>>(__VA_ARGS__)
 #define ICER_LAUNCH_WAVE_ON(stream, kernel, grid, shmem, ...) kernel<<<(grid), 64, (shmem), (stream)>>>(__VA_ARGS__)
+#define ICER_LAUNCH_ON(stream, kernel, grid, block, shmem, ...) kernel<<<(grid), (block), (shmem), (stream)>>>(__VA_ARGS__)
+#define ICER_LAUNCH_PLANES_ON(stream, kernel, grid, shmem, ...) kernel<<<(grid), 64 * kPwWaves, (shmem), (stream)>>>(__VA_ARGS__)
 #define ICER_DYNAMIC_LDS(T, name) extern __shared__ T name[]
 // the decoder tables of a workgroup: a copy in LDS (every decision looks them up; from global memory each look-up is a
 // chain of dependent loads)
@@ -37,6 +42,9 @@
 #include <vector>
 
 #include "../../include/icer_hip_dec.h"
+#if !defined(ICER_HOST_MOCK) || defined(ICER_MOCK_ASYNC)
+#define ICER_DECODE_ASYNC 1            // icerx_decode_device_async (decoder_async.hpp; the CPU mock needs tests/emu/hip_mock_async.h)
+#endif
 #include "decoder_wave.hpp"
 #include "decoder_planes.hpp"
 #include "decoder_core.hpp"
@@ -289,6 +297,13 @@ struct icerx_decoder {
     static constexpr int kRingClasses = 4;
     hipStream_t side[kRingClasses] = {};
     bool side_ok = false;
+    // icerx_decode_device_async: the events that fork its side-stream work from the caller's stream and join it back, and
+    // whether its planes kernel has been granted the LDS that resolve_planes_lds found
+#ifdef ICER_DECODE_ASYNC
+    hipEvent_t fork = nullptr, join[kRingClasses] = {};
+    bool events_ok = false;
+#endif
+    int async_lds_state = 0;           // 0: not asked yet, 1: granted, -1: refused (the async planes kernel keeps 48 KiB)
 };
 
 namespace {
@@ -300,6 +315,55 @@ hipError_t ensure(icerx_decoder::Buf &b, size_t bytes)
     const hipError_t e = hipMalloc(&b.p, bytes);
     if (e == hipSuccess) b.cap = bytes;
     return e;
+}
+
+// The dynamic LDS the wave-per-plane kernel may take on this decoder's device (asked once per decoder; granted to
+// decode_chains_planes_kernel on the way)
+size_t resolve_planes_lds(icerx_decoder *d)
+{
+#ifdef ICER_HOST_MOCK
+    (void)d;
+    return (size_t)1 << 20;
+#else
+    // what a workgroup of this device may take (gfx950: 160 KiB), less 10 KiB for the kernel's static block and the runtime
+    size_t planes_lds_limit = 0;
+    int max_lds = 0, dev_id = d->device;
+    if (dev_id < 0 && hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); dev_id = 0; }      // (-1: the caller's current device)
+    if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) { (void)hipGetLastError(); max_lds = 64 * 1024; }
+    // (this runtime reports 64 KiB for gfx950, whose compute units have 160 KiB and grant a workgroup what hipFuncSetAttribute asks for --
+    // the encoder's window coder runs on 115 KiB --: ask for the hardware's figure first, the reported one is the fall-back)
+    if (d->is_gfx950 < 0) {
+        hipDeviceProp_t prop;
+        d->is_gfx950 = (hipGetDeviceProperties(&prop, dev_id) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) ? 1 : 0;
+        (void)hipGetLastError();
+    }
+    const bool gfx950 = d->is_gfx950 == 1;
+    if (gfx950 && max_lds < 160 * 1024 && !d->planes_lds_refused) max_lds = 160 * 1024;
+    planes_lds_limit = max_lds > 10 * 1024 ? (size_t)max_lds - 10u * 1024u : 0u;
+    // more than 48 KiB of dynamic LDS has to be granted; a runtime / device that refuses loses nothing but the fast kernel
+    // for the chains that need it (they go to decode_chains_wave_kernel below)
+    if (planes_lds_limit > 48u * 1024u && !d->planes_lds_raised && !d->planes_lds_refused) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(decode_chains_planes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes_lds_limit) == hipSuccess)
+            d->planes_lds_raised = true;
+        else {
+            (void)hipGetLastError(); d->planes_lds_refused = true;
+            int rep = 0;
+            if (hipDeviceGetAttribute(&rep, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) { (void)hipGetLastError(); rep = 64 * 1024; }
+            planes_lds_limit = rep > 10 * 1024 ? (size_t)rep - 10u * 1024u : 0u;
+            if (planes_lds_limit > 48u * 1024u && hipFuncSetAttribute(reinterpret_cast<const void *>(decode_chains_planes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes_lds_limit) == hipSuccess)
+                d->planes_lds_fallback = planes_lds_limit;
+            else (void)hipGetLastError();
+        }
+        // (said once per decoder: on a runtime that reports or grants less than gfx950's 160 KiB the fast planes kernel quietly loses
+        // the chains that need more -- correct, slower)
+        if (d->planes_lds_refused || planes_lds_limit < 150u * 1024u)
+            fprintf(stderr, "libicer_hip_dec: %zu KiB of LDS per workgroup for the planes kernel (%s); chains that need more take the wave kernel\n",
+                    (d->planes_lds_refused ? (d->planes_lds_fallback ? d->planes_lds_fallback : (size_t)48u * 1024u) : planes_lds_limit) / 1024u,
+                    d->planes_lds_refused ? "the runtime refused the hardware's 150 KiB" : "what the device reports, less 10 KiB");
+    }
+    if (d->planes_lds_refused) planes_lds_limit = d->planes_lds_fallback ? d->planes_lds_fallback : std::min(planes_lds_limit, (size_t)48u * 1024u);
+    return planes_lds_limit;
+#endif
 }
 
 // n streams: stream k = bytes [offsets[k], offsets[k] + lens[k]) of `data` (host memory, or device memory when
@@ -426,49 +490,7 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
         const bool want_planes = !(mode && (mode[0] == '0' || mode[0] == '1')) && d->tables.lut_ok != 0u &&
                                  (!by_load || n_eligible <= 12u * (size_t)d->n_cus);
         size_t planes_lds = 0;
-#ifdef ICER_HOST_MOCK
-        const size_t planes_lds_limit = (size_t)1 << 20;
-#else
-        // what a workgroup of this device may take (gfx950: 160 KiB), less 10 KiB for the kernel's static block and the runtime
-        size_t planes_lds_limit = 0;
-        {
-            int max_lds = 0, dev_id = d->device;
-            if (dev_id < 0 && hipGetDevice(&dev_id) != hipSuccess) { (void)hipGetLastError(); dev_id = 0; }      // (-1: the caller's current device)
-            if (hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) { (void)hipGetLastError(); max_lds = 64 * 1024; }
-            // (this runtime reports 64 KiB for gfx950, whose compute units have 160 KiB and grant a workgroup what hipFuncSetAttribute asks for --
-            // the encoder's window coder runs on 115 KiB --: ask for the hardware's figure first, the reported one is the fall-back)
-            if (d->is_gfx950 < 0) {
-                hipDeviceProp_t prop;
-                d->is_gfx950 = (hipGetDeviceProperties(&prop, dev_id) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0) ? 1 : 0;
-                (void)hipGetLastError();
-            }
-            const bool gfx950 = d->is_gfx950 == 1;
-            if (gfx950 && max_lds < 160 * 1024 && !d->planes_lds_refused) max_lds = 160 * 1024;
-            planes_lds_limit = max_lds > 10 * 1024 ? (size_t)max_lds - 10u * 1024u : 0u;
-            // more than 48 KiB of dynamic LDS has to be granted; a runtime / device that refuses loses nothing but the fast kernel
-            // for the chains that need it (they go to decode_chains_wave_kernel below)
-            if (planes_lds_limit > 48u * 1024u && !d->planes_lds_raised && !d->planes_lds_refused) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(decode_chains_planes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes_lds_limit) == hipSuccess)
-                    d->planes_lds_raised = true;
-                else {
-                    (void)hipGetLastError(); d->planes_lds_refused = true;
-                    int rep = 0;
-                    if (hipDeviceGetAttribute(&rep, hipDeviceAttributeMaxSharedMemoryPerBlock, dev_id) != hipSuccess) { (void)hipGetLastError(); rep = 64 * 1024; }
-                    planes_lds_limit = rep > 10 * 1024 ? (size_t)rep - 10u * 1024u : 0u;
-                    if (planes_lds_limit > 48u * 1024u && hipFuncSetAttribute(reinterpret_cast<const void *>(decode_chains_planes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes_lds_limit) == hipSuccess)
-                        d->planes_lds_fallback = planes_lds_limit;
-                    else (void)hipGetLastError();
-                }
-                // (said once per decoder: on a runtime that reports or grants less than gfx950's 160 KiB the fast planes kernel quietly loses
-                // the chains that need more -- correct, slower)
-                if (d->planes_lds_refused || planes_lds_limit < 150u * 1024u)
-                    fprintf(stderr, "libicer_hip_dec: %zu KiB of LDS per workgroup for the planes kernel (%s); chains that need more take the wave kernel\n",
-                            (d->planes_lds_refused ? (d->planes_lds_fallback ? d->planes_lds_fallback : (size_t)48u * 1024u) : planes_lds_limit) / 1024u,
-                            d->planes_lds_refused ? "the runtime refused the hardware's 150 KiB" : "what the device reports, less 10 KiB");
-            }
-            if (d->planes_lds_refused) planes_lds_limit = d->planes_lds_fallback ? d->planes_lds_fallback : std::min(planes_lds_limit, (size_t)48u * 1024u);
-        }
-#endif
+        const size_t planes_lds_limit = resolve_planes_lds(d);
         std::stable_partition(chains.begin(), chains.end(), [&](const ChainDesc &c) {
             return want_planes && c.fast && frames[c.frame].stream_len >= 4u && pw_lds_bytes(c.w, nplanes) <= planes_lds_limit; });
         uint32_t n_fast = 0;
@@ -662,6 +684,10 @@ int decompress_planes(void *const planes[], int channels, size_t *image_w, size_
 
 }  // namespace
 
+#ifdef ICER_DECODE_ASYNC
+#include "decoder_async.hpp"
+#endif
+
 extern "C" {
 
 const char *icerx_decoder_last_error(void) { return g_error.c_str(); }
@@ -711,6 +737,12 @@ void icerx_decoder_destroy(icerx_decoder *d)
 #ifndef ICER_HOST_MOCK
     if (d->side_ok) for (hipStream_t st : d->side) (void)hipStreamDestroy(st);
 #endif
+#ifdef ICER_DECODE_ASYNC
+    if (d->events_ok) {
+        (void)hipEventDestroy(d->fork);
+        for (hipEvent_t e : d->join) (void)hipEventDestroy(e);
+    }
+#endif
     delete d;
 }
 
@@ -727,6 +759,22 @@ int icerx_decode_device(icerx_decoder *dec, int n, const void *d_data, const siz
     if (!d_out && n) return ICER_INVALID_INPUT;
     return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, nullptr, d_out, frame_stride, rcs, ws, hs);
 }
+
+#ifdef ICER_DECODE_ASYNC
+size_t icerx_decode_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t frame_stride)
+{
+    if (!dec || n <= 0) return 0;
+    return async_layout(dec, n, data_bytes, frame_stride).total;
+}
+
+int icerx_decode_device_async(icerx_decoder *dec, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                              size_t stream_stride, const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs,
+                              uint64_t *d_ws, uint64_t *d_hs, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return decode_async(dec, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, d_out, frame_stride, d_rcs,
+                        d_ws, d_hs, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+#endif
 
 int icer_get_image_dimensions(const uint8_t *datastream, size_t data_length, size_t *image_w, size_t *image_h)
 {

@@ -736,8 +736,9 @@ ICER_HD int32_t dec_floordiv(int32_t a, int32_t b)            // icer_floor_div_
 // src: [lows | highs] of a line of n samples (stride in samples); dst: the samples, value v of the [lows | highs]
 // layout going to position pos_of[v] (the plain interleave, except for the uint8 routine's odd lines -- see
 // interleave_positions).  `bits` = 8: int8 storage (truncating stores), icer_wavelet.c:298-383.
-ICER_HD void idwt_line(const int16_t *src, int16_t *dst, uint32_t n, size_t stride, const FilterTaps f, int bits,
-                       const uint32_t *pos_of)
+// `pos`: a position functor, pos(v) = pos_of[v] (PosTable) or computed (decoder_dplan.hpp DPos)
+template <class Pos>
+ICER_HD void idwt_line_at(const int16_t *src, int16_t *dst, uint32_t n, size_t stride, const FilterTaps f, int bits, Pos pos_of)
 {
     const uint32_t nl = (n + 1u) / 2u, nh = n / 2u;
     const bool odd = (n & 1u) != 0;
@@ -763,10 +764,47 @@ ICER_HD void idwt_line(const int16_t *src, int16_t *dst, uint32_t n, size_t stri
         const int32_t hi = TR(HI(k) + add);
         next_hi = hi;
         const int32_t a = LO(k) + dec_floordiv(hi + 1, 2);
-        dst[(size_t)pos_of[k] * stride] = TR(a);
-        dst[(size_t)pos_of[nl + k] * stride] = TR(a - hi);
+        dst[(size_t)pos_of(k) * stride] = TR(a);
+        dst[(size_t)pos_of(nl + k) * stride] = TR(a - hi);
     }
-    if (odd) dst[(size_t)pos_of[nl - 1u] * stride] = (int16_t)LO(nl - 1u);
+    if (odd) dst[(size_t)pos_of(nl - 1u) * stride] = (int16_t)LO(nl - 1u);
+#undef LO
+#undef HI
+#undef RR
+#undef TR
+}
+struct PosTable {
+    const uint32_t *pos_of;
+    ICER_HD uint32_t operator()(uint32_t v) const { return pos_of[v]; }
+};
+ICER_HD void idwt_line(const int16_t *src, int16_t *dst, uint32_t n, size_t stride, const FilterTaps f, int bits,
+                       const uint32_t *pos_of)
+{
+    idwt_line_at(src, dst, n, stride, f, bits, PosTable{pos_of});
+}
+
+// Output pair k of a line of a filter without a recurrence along it (beta = 0 and alpha_-1 = 0: filter A -- every restored
+// high then depends on the stored lows and highs alone, idwt_line's `dn` and filter-C terms drop out); k = nh: the last low
+// of an odd line.  (decoder.hip's idwt_pairs_kernel keeps its own copy of this body: calling it from there changes that
+// kernel's code.)
+template <class Pos>
+ICER_HD void idwt_pair_at(const int16_t *s, int16_t *d, uint32_t n, size_t stride, uint32_t k, const FilterTaps f, int bits, Pos pos_of)
+{
+    const uint32_t nl = (n + 1u) / 2u, nh = n / 2u;
+    const bool odd = (n & 1u) != 0;
+#define LO(i) ((int32_t)s[(size_t)(i) * stride])
+#define HI(i) ((int32_t)s[(size_t)(nl + (i)) * stride])
+#define RR(i) ((int32_t)(int16_t)(LO((i) - 1) - LO(i)))
+#define TR(v) (bits == 8 ? (int16_t)(int8_t)(v) : (int16_t)(v))
+    if (k >= nh) { d[(size_t)pos_of(nl - 1u) * stride] = (int16_t)LO(nl - 1u); return; }
+    int32_t add;
+    if (k == 0) add = dec_floordiv(RR(1), 4);
+    else if (!odd && k == nh - 1u) add = dec_floordiv(RR(nh - 1u), 4);
+    else add = dec_floordiv(f.a0 * RR(k) + f.a1 * RR(k + 1u) + 8, 16);
+    const int32_t hi = TR(HI(k) + add);
+    const int32_t a = LO(k) + dec_floordiv(hi + 1, 2);
+    d[(size_t)pos_of(k) * stride] = TR(a);
+    d[(size_t)pos_of(nl + k) * stride] = TR(a - hi);
 #undef LO
 #undef HI
 #undef RR

@@ -89,6 +89,13 @@ class Decoder:
         tail = [C.POINTER(_sz), C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(C.c_int), C.POINTER(_sz), C.POINTER(_sz)]
         self.lib.icerx_decode_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + tail
         self.lib.icerx_decode_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + tail
+        if hasattr(self.lib, "icerx_decode_device_async"):
+            self.lib.icerx_decode_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, _sz]
+            self.lib.icerx_decode_workspace_bytes.restype = _sz
+            self.lib.icerx_decode_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p,
+                                                           C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
+                                                           C.c_void_p]
+        self._workspaces = {}                # decode_torch: one cached workspace per torch stream
         self.handle = C.c_void_p()
         rc = self.lib.icerx_decoder_create(C.byref(self.handle), device, channels, stages, filt, segments, bits)
         if rc != 0:
@@ -130,6 +137,61 @@ class Decoder:
         rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
         rc = self.lib.icerx_decode_device(self.handle, n, d_data, offs, ln, d_out, frame_stride, rcs, ws, hs)
         return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+
+    def workspace_bytes(self, n: int, data_bytes: int, frame_stride: int) -> int:
+        """icerx_decode_workspace_bytes: the device workspace one decode_device_async_ptrs call needs"""
+        return int(self.lib.icerx_decode_workspace_bytes(self.handle, n, data_bytes, frame_stride))
+
+    def decode_device_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, d_out: int,
+                                 frame_stride: int, d_rcs: int, d_ws: int, d_hs: int, d_workspace: int, workspace_bytes: int,
+                                 stream: int = 0) -> int:
+        """icerx_decode_device_async on raw device pointers (d_offsets None: stream k starts at k * stream_stride; offsets,
+        lens, ws, hs: uint64 / int64; rcs: int32).  Enqueues on `stream` and returns the call's rc without waiting."""
+        return self.lib.icerx_decode_device_async(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_out,
+                                                  frame_stride, d_rcs, d_ws, d_hs, d_workspace, workspace_bytes, stream)
+
+    def decode_torch(self, data, lens, out, rcs, ws, hs, offsets=None, stream_stride=None) -> None:
+        """Decode n streams of a cuda uint8 tensor on torch's current stream, without waiting (icerx_decode_device_async).
+
+        data: the blob, 1-D, or 2-D (n, stride) with stream k in row k; lens / offsets: cuda int64 (n,), offsets None: stream
+        k starts at k * stream_stride (default: data.stride(0) of a 2-D blob); out: cuda int16 / uint16 (uint8 for an 8-bit decoder),
+        n * channels * frame_stride samples, e.g. (n, channels, frame_stride); rcs: cuda int32 (n,); ws / hs: cuda int64 (n,),
+        read as the sizes kept by a stream without a valid packet and written with each frame's size.  The workspace is
+        cached per stream and grown here, on the host, before the call is enqueued.
+
+        The encoder's output goes in as it is, with nothing copied to the host:
+            enc.encode_torch(frames, quota, out=streams, sizes=sizes, rcs=enc_rcs)          # streams: (n, out_stride) uint8
+            dec.decode_torch(streams, sizes, planes, rcs, ws, hs)                            # offsets = k * out_stride
+            torch.cuda.current_stream().synchronize()
+        """
+        import torch
+        n = int(lens.shape[0])
+        if offsets is None and stream_stride is None:
+            if data.dim() != 2:
+                raise ValueError("a 1-D blob needs offsets or stream_stride")
+            stream_stride = data.stride(0)
+        want = (torch.int16, getattr(torch, "uint16", torch.int16)) if self.bits == 16 else (torch.uint8,)
+        for name, t, dts in (("data", data, (torch.uint8,)), ("lens", lens, (torch.int64,)), ("rcs", rcs, (torch.int32,)),
+                             ("ws", ws, (torch.int64,)), ("hs", hs, (torch.int64,)), ("out", out, want)) + \
+                ((("offsets", offsets, (torch.int64,)),) if offsets is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype not in dts:
+                raise ValueError(f"{name}: a contiguous cuda {dts[0]} tensor is needed")
+        if n and out.numel() % (n * self.channels):
+            raise ValueError("out must hold n * channels * frame_stride samples")
+        frame_stride = out.numel() // (n * self.channels) if n else 0
+        data_bytes = data.numel()
+        st = torch.cuda.current_stream(data.device)
+        need = self.workspace_bytes(n, data_bytes, frame_stride) if n else 0
+        work = self._workspaces.get(st.cuda_stream)
+        if work is None or work.numel() < max(need, 1):
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
+            self._workspaces[st.cuda_stream] = work
+        work.record_stream(st)
+        rc = self.decode_device_async_ptrs(n, data.data_ptr(), data_bytes, offsets.data_ptr() if offsets is not None else None,
+                                           int(stream_stride or 0), lens.data_ptr(), out.data_ptr(), frame_stride, rcs.data_ptr(),
+                                           ws.data_ptr(), hs.data_ptr(), work.data_ptr(), work.numel(), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_decode_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
 
 
 # ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------

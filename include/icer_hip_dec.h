@@ -79,6 +79,27 @@ int icerx_decode_host(icerx_decoder *dec, int n, const uint8_t *data, const size
 int icerx_decode_device(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
                         void *d_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs);
 
+/* Stream-ordered twin of icerx_decode_device: every input and output per frame is in device memory, everything is planned
+ * on the GPU (decoder_async.hpp), and the call only enqueues work on `stream` (a hipStream_t; NULL: the null stream) and
+ * returns.  It makes no blocking copy, no stream or device synchronisation and no hipMalloc / hipFree.
+ *   stream k = d_data[off_k, off_k + d_lens[k]), off_k = d_offsets[k], or k * stream_stride when d_offsets is NULL (the
+ *   encoder's d_out / out_stride / d_sizes plug in unchanged).  d_ws / d_hs are read as the in-values of the synchronous call.
+ *   Frame k's outputs d_out, d_rcs[k], d_ws[k], d_hs[k] equal those of icerx_decode_device on the same streams.  A frame
+ *   whose bytes leave [0, data_bytes) gets ICER_INVALID_INPUT and is not decoded; a wave-per-plane chain past its spin
+ *   bound (an internal error; the synchronous call fails as a whole) gives its frame ICER_FATAL_ERROR.
+ * The workspace (device memory, owned by the caller) holds at least icerx_decode_workspace_bytes(dec, n, data_bytes,
+ * frame_stride) bytes: about 4 bytes per blob byte for the packet candidates (at most ceil(data_bytes / 2) of 8 bytes each)
+ * plus 2 bytes per output sample (4 for 8-bit decoders) and a per-frame packet table.  It and every buffer passed in must
+ * stay untouched until the work has completed on `stream`.  The call returns ICER_INVALID_INPUT for null arguments or a
+ * workspace that is too small, ICER_FATAL_ERROR for data_bytes or frame_stride past the 32-bit limits of the synchronous
+ * call (nothing is enqueued then).  Part of the work runs on the decoder's side streams, forked from `stream` and joined
+ * back to it with events: once `stream` has completed, so has the call.  Calls on different streams may be in flight
+ * together, each with its own workspace; the decoder object itself is not thread-safe. */
+size_t icerx_decode_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t frame_stride);
+int icerx_decode_device_async(icerx_decoder *dec, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                              size_t stream_stride, const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs,
+                              uint64_t *d_ws, uint64_t *d_hs, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* last error message of this thread's most recent failing call ("" if none) */
 const char *icerx_decoder_last_error(void);
 
