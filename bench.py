@@ -16,7 +16,8 @@ when it has one: step k is submitted before step k - 1 is waited for, everything
 frames' pixels x steps / max-over-ranks time.  Its N = 1 point is `scaling_reference` of the --gpus 1 line (whose own `value` is the lone C2 frame).  --config C2 --gpus N:
 every rank its own copy of the C2 frame (weak).
 
-Secondary objects of the same line (none of them is `value`):
+A plain run is the headline alone: set-up, parity gate, warm-up, the timed steps, --dump-outputs when given, the result line.
+Everything else it can measure comes with --full, which adds these secondary objects to the same line (none of them is `value`):
   batched        C2 geometry, 8 frames per launch
   batch_configs  this GPU's share of the two batch configurations BASELINE.json names for 8 GPUs: "C4" = 256 x 2048x2048
                  (32 frames per GPU, frames 32*rank ..), "C5" = 64 x 8192x8192 (8 per GPU); every frame of every rank is
@@ -41,7 +42,8 @@ Secondary objects of the same line (none of them is `value`):
 8-GPU job in turn on this one GPU (all 256 / 64 frames, each against its reference golden); with --scaling strong the
 whole batch is split over the ranks (N = 1: all of it on one GPU); --source host times the host-fed path instead.
 
-    python bench.py                       # 1 GPU
+    python bench.py                       # 1 GPU, the headline alone
+    python bench.py --full                # ... and every secondary object
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -866,6 +868,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (return codes, stream lengths, CRC-32s, stream bytes) "
                          "as DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true", help="also measure every secondary object of the line (batch configurations, host-fed "
+                    "and streaming legs, C3, decode, drop-in, CPU baselines, rocprofv3 passes, ...); the --no-* options, --batched-probe and "
+                    "--all-extras choose among them.  Without it a run is the headline alone")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -873,6 +878,10 @@ def main():
         raise SystemExit("--steps must be >= 1")
     if args.dump_outputs and args.sweep:
         raise SystemExit("--dump-outputs needs the timed workload; --sweep times every share in turn")
+    if not args.full:
+        # the headline alone: every secondary leg below is off (c2_per_rank and host_fed of an N > 1 line check args.full themselves)
+        args.no_cpu_baseline = args.no_batch_configs = args.no_traffic = args.no_extras = args.no_one_process = True
+        args.batched_probe = 0
     # N > 1: the whole C4 batch (256 frames, BASELINE configs[3]: what north_star says scales) split over the ranks, every frame
     # checked; the lone C2 frame per rank is a secondary object of that line.  N = 1: C2, the configuration the metric is quoted on.
     if args.config is None:
@@ -1181,7 +1190,7 @@ def main():
     # secondary objects of an N > 1 line whose headline is a batch: the lone C2 frame on every rank; at N = 1 (headline C2): the
     # WHOLE C4 batch on this one GPU -- the N = 1 point of the strong-scaling curve the N > 1 lines continue
     c2_rank = scaling_ref = None
-    if device_wl and have_bg:
+    if device_wl and have_bg and args.full:
         if world > 1 and args.config != "C2":
             try:
                 c2_rank = c2_per_rank_object(rank, dev, local_rank, barrier, all_ranks_ok, world, red_dev)
@@ -1207,7 +1216,7 @@ def main():
     # streams in page-locked host memory) beside the device-resident headline -- at 8 GPUs the ranks share the host's DRAM and PCIe root
     # (about 270 MB in and 80 MB out per rank and step of 32 frames), so this is the curve that can bend first
     host_fed = None
-    if world > 1 and args.config != "C2" and args.scaling == "strong" and device_wl and have_bg:
+    if args.full and world > 1 and args.config != "C2" and args.scaling == "strong" and device_wl and have_bg:
         try:
             lo, hi = shard.shard_range(cfg["total"], rank, world)
             hw = HostWorkload(args.config, rank, dev, local_rank, first=lo, count=hi - lo)

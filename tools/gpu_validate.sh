@@ -5,7 +5,7 @@
 set -u
 T=${1:-validate}; O=gpurun_out/$T; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 timeout 400 bash tools/profile_round.sh ${T}_prof > $O/profile_round.log 2>&1
 timeout 200 python tools/phase_profile.py > $O/phase_pipe.log 2>&1
 mkdir -p $O/profiles_new; cp profiles/${T}_prof* profiles/latest_pmc.json $O/profiles_new/ 2>/dev/null

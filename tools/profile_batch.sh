@@ -15,7 +15,7 @@ timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$out/pmc_fetch" -o r -
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$out/pmc_write" -o r -- $B > /dev/null 2> "$out/pmc_write.err"
 cd "$root"
 python tools/rocprof_summary.py "${tag}_$cfg" "$out/stats/r_results.db" "$out/pmc_fetch/r_results.db" "$out/pmc_write/r_results.db"
-timeout 900 python bench.py --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --batched-probe 0 --no-batch-configs --no-extras --no-one-process > "profiles/${tag}_${cfg}_bench.json" 2> "$out/bench.err"
+timeout 900 python bench.py --full --config $cfg --steps 5 --warmup 1 --no-cpu-baseline --batched-probe 0 --no-batch-configs --no-extras --no-one-process > "profiles/${tag}_${cfg}_bench.json" 2> "$out/bench.err"
 mkdir -p "$root/gpurun_out/${tag}_summaries"
 cp "profiles/${tag}_${cfg}_rocprof.json" "profiles/${tag}_${cfg}_rocprof.md" "profiles/${tag}_${cfg}_bench.json" "$root/gpurun_out/${tag}_summaries/"
 rm -rf "$out/stats" "$out/pmc_fetch" "$out/pmc_write"
