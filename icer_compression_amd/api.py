@@ -79,6 +79,8 @@ def load_library() -> C.CDLL:
     L.icerx_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                       C.c_void_p, C.c_void_p]
     L.icerx_encode_device_async.argtypes = L.icerx_encode_device.argtypes
+    L.icerx_encode_device_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
     L.icerx_encoder_wait.argtypes = [C.c_void_p]
     L.icerx_compress_batch_uint16.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
@@ -235,6 +237,39 @@ class Encoder:
         st = torch.cuda.current_stream(frames.device).cuda_stream
         self.encode_device_ptrs(frames.data_ptr(), n, byte_quota, out.data_ptr(), out.stride(0), sizes.data_ptr(),
                                 rcs.data_ptr(), st)
+
+    def encode_ladder_ptrs(self, d_frames: int, n_frames: int, quotas, d_out: int, out_stride: int, d_sizes: int, d_rcs: int,
+                           stream: int = 0) -> None:
+        """icerx_encode_device_ladder: the frames at every quota of `quotas` (at most ICERX_MAX_LADDER) in one call; frame f at
+        quotas[q] goes to row q * n_frames + f of d_out and entry q * n_frames + f of d_sizes / d_rcs"""
+        qs = [int(q) for q in quotas]
+        arr = (C.c_size_t * max(len(qs), 1))(*qs)
+        rc = self.lib.icerx_encode_device_ladder(self.handle, d_frames, n_frames, arr, len(qs), d_out, out_stride, d_sizes, d_rcs,
+                                                 stream)
+        if rc != 0:
+            raise IcerHipError(f"icerx_encode_device_ladder rc={rc}: {self.lib.icerx_last_error().decode()}")
+
+    def encode_ladder_torch(self, frames, quotas, out=None, sizes=None, rcs=None):
+        """frames: cuda tensor (n, channels, h, w) or (n, h, w) -- int16/uint16, or uint8 (int8 storage) for an encoder of
+        sample_bits 8.  Codes them once at every quota of `quotas` on torch's current stream.  out: cuda uint8 (Q, n, stride),
+        sizes: cuda int64 (Q, n), rcs: cuda int32 (Q, n), allocated (stride = the largest quota) when not given.  Returns
+        (out, sizes, rcs)."""
+        import torch
+        n, Q = frames.shape[0], len(quotas)
+        dev = frames.device
+        if out is None:
+            out = torch.empty((Q, n, max(int(q) for q in quotas)), dtype=torch.uint8, device=dev)
+        if sizes is None:
+            sizes = torch.empty((Q, n), dtype=torch.int64, device=dev)
+        if rcs is None:
+            rcs = torch.empty((Q, n), dtype=torch.int32, device=dev)
+        if out.dim() != 3 or tuple(out.shape[:2]) != (Q, n) or out.stride(2) != 1 or out.stride(0) != n * out.stride(1):
+            raise ValueError("out must be a uint8 tensor (Q, n, stride) whose rows are stride bytes apart")
+        if tuple(sizes.shape) != (Q, n) or tuple(rcs.shape) != (Q, n) or not sizes.is_contiguous() or not rcs.is_contiguous():
+            raise ValueError("sizes and rcs must be contiguous tensors (Q, n)")
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.encode_ladder_ptrs(frames.data_ptr(), n, quotas, out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(), st)
+        return out, sizes, rcs
 
     def encode_torch_s8(self, planes, byte_quota: int):
         """uint8 twins: planes = cuda uint8 tensor (n, h, w) or (n, channels, h, w), int8 storage; the encoder must have

@@ -431,12 +431,22 @@ const char *pool_compute_level() { const char *v = getenv("ICER_HIP_COMPUTE_LEVE
 constexpr int kLonePadBytes = ICER_LONE_PAD_BYTES;      // LDS padding of the pipeline's workgroups in a split launch (launch_plan.hpp PipeKernel::Lone)
 static_assert(kUnitWavesSmall == 8 && kUnitWavesLarge == 11, "launch_plan.hpp names the pipeline's shapes by these wave counts");
 
+// The quotas of a rate ladder call (icerx_encode_device_ladder): the batch is planned and coded for the largest one, and each
+// quota's stream is cut from it (assemble_ladder.hpp).  A ladder of one quota is an ordinary call at that quota.
+struct Ladder {
+    LadderQuotas quotas;
+    int n = 0;              // quotas
+    int pitch = 0;          // frames of the call: the rows of one quota's block of the output
+};
+static_assert(kMaxLadder == ICERX_MAX_LADDER, "assemble_ladder.hpp and include/icer_hip.h agree on the ladder's length");
+
 // enqueue the whole pipeline for part `part` of the call `lp` -- the frames [f0, f0 + n_frames) of a batch -- on `st` (d_frames,
 // d_out, d_sizes, d_rcs: of frame f0); every per-frame buffer of the encoder is used from frame f0 on, so that parts of a batch can
 // be in flight on different streams (enqueue).  `part` also names the set of per-launch resources (route list cursor, fork / join
-// events) it takes; `timed`: it records the stage events.  Returns 0 or ICER_FATAL_ERROR.
+// events) it takes; `timed`: it records the stage events.  `ladder` (several quotas): the part's frames are cut at each of them, into
+// their rows of every quota's block (`quota` is the largest).  Returns 0 or ICER_FATAL_ERROR.
 int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, const uint16_t *d_frames, size_t quota, uint8_t *d_out, size_t out_stride,
-                 unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool clear_bound)
+                 unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool clear_bound, const Ladder *ladder = nullptr)
 {
     const PartPlan &pp = lp.part[part];
     const int f0 = pp.f0, n_frames = pp.n_frames;
@@ -566,10 +576,19 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
     if (timed && e->timing) HIP_TRY(hipEventRecord(e->ev[3], st));
 
     // ---- quota scan + gather into final stream order
-    hipLaunchKernelGGL(scan_kernel, dim3(n_frames), dim3(64), 0, st, unit_bits, e->final_order.p, n_units,
-                       (uint64_t)quota, skip, final_off, d_sizes, d_rcs, e->units.p, bound_ovf);
-    hipLaunchKernelGGL(gather_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
-                       e->units.p, n_units, unit_bits, final_off, d_out, out_stride);
+    if (!ladder || ladder->n == 1) {
+        hipLaunchKernelGGL(scan_kernel, dim3(n_frames), dim3(64), 0, st, unit_bits, e->final_order.p, n_units,
+                           (uint64_t)quota, skip, final_off, d_sizes, d_rcs, e->units.p, bound_ovf);
+        hipLaunchKernelGGL(gather_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
+                           e->units.p, n_units, unit_bits, final_off, d_out, out_stride);
+    } else {
+        // (the final offsets of quota q: the q-th block of max_frames x units entries, icerx_encode_device_ladder sized them)
+        const size_t off_pitch = (size_t)e->max_frames * n_units;
+        hipLaunchKernelGGL(scan_ladder_kernel, dim3(n_frames, ladder->n), dim3(64), 0, st, unit_bits, e->final_order.p, n_units,
+                           ladder->quotas, skip, final_off, off_pitch, d_sizes, d_rcs, (uint32_t)ladder->pitch, e->units.p, bound_ovf);
+        hipLaunchKernelGGL(gather_ladder_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
+                           e->units.p, n_units, unit_bits, final_off, off_pitch, (uint32_t)ladder->n, d_out, out_stride, (uint32_t)ladder->pitch);
+    }
     if (timed && e->timing) {
         HIP_TRY(hipEventRecord(e->ev[4], st));
         e->ev_pending = true;
@@ -584,13 +603,13 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
 // behind the next part's: what a caller gets from two encoders and the asynchronous calls, inside one call.  Not for
 // the asynchronous entry points (the caller overlaps whole batches itself), progressive mode, or single frames.
 int enqueue(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t quota, uint8_t *d_out, size_t out_stride,
-            unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool overlap_ok)
+            unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool overlap_ok, const Ladder *ladder = nullptr)
 {
     const int C = e->channels;
     int *bound_ovf = e->flags.p + 2 * (size_t)e->max_frames * C + e->max_frames;
     const CoderState cs{e->wg_available, e->wg_once, e->half_stream != nullptr};
     const LaunchPlan &lp = e->last_plan = plan_launch(launch_shape(e), e->tuning, cs, n_frames, quota, overlap_ok);
-    if (lp.n_parts == 1) return enqueue_part(e, lp, 0, true, d_frames, quota, d_out, out_stride, d_sizes, d_rcs, st, true);
+    if (lp.n_parts == 1) return enqueue_part(e, lp, 0, true, d_frames, quota, d_out, out_stride, d_sizes, d_rcs, st, true, ladder);
     const size_t plane = e->w * e->h;
     HIP_TRY(hipMemsetAsync(bound_ovf, 0, sizeof(int), st));             // (shared by the parts: before the second stream forks off)
     HIP_TRY(hipEventRecord(e->part_fork, st));                          // (the second stream starts behind whatever the caller's stream holds)
@@ -601,7 +620,7 @@ int enqueue(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t quo
         const int f0 = lp.part[k].f0;
         hipStream_t ps = (k & 1) ? e->half_stream : st;
         if (int rc = enqueue_part(e, lp, k, false, d_frames + (size_t)f0 * C * plane, quota, d_out + (size_t)f0 * out_stride, out_stride,
-                                  d_sizes + f0, d_rcs + f0, ps, false)) return rc;
+                                  d_sizes + f0, d_rcs + f0, ps, false, ladder)) return rc;
     }
     HIP_TRY(hipEventRecord(e->part_join, e->half_stream));
     HIP_TRY(hipStreamWaitEvent(st, e->part_join, 0));
@@ -769,9 +788,10 @@ static void report_timeouts(icerx_encoder *e, int n_frames)
 
 // One encode call = begin (everything enqueued on the stream, nothing waited for) + finish (wait, then the rare re-runs).
 // `flag` = two pinned host words that receive the batch's verdict: [0] bit 0 a coding unit outgrew its provisioned slot,
-// bit 1 a unit timed out; [1] units on the route list.
+// bit 1 a unit timed out; [1] units on the route list.  `ladder`: a rate ladder call, byte_quota its largest quota.
 static int encode_begin(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
-                        size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, hipStream_t st, int *flag, hipEvent_t done, bool *regrow, bool overlap_ok = false)
+                        size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, hipStream_t st, int *flag, hipEvent_t done, bool *regrow, bool overlap_ok = false,
+                        const Ladder *ladder = nullptr)
 {
     if (upload_units(e, byte_quota, st)) return ICER_FATAL_ERROR;
     if (e->slots.ensure((size_t)e->max_frames * e->plan.slot_bytes)) return ICER_FATAL_ERROR;
@@ -781,7 +801,7 @@ static int encode_begin(icerx_encoder *e, const uint16_t *d_frames, int n_frames
         return ICER_INVALID_INPUT;
     }
     int *bound_ovf = e->flags.p + 2 * (size_t)e->max_frames * e->channels + e->max_frames;
-    if (enqueue(e, d_frames, n_frames, byte_quota, d_out, out_stride, (unsigned long long *)d_sizes, d_rcs, st, overlap_ok && flag == e->h_flag))
+    if (enqueue(e, d_frames, n_frames, byte_quota, d_out, out_stride, (unsigned long long *)d_sizes, d_rcs, st, overlap_ok && flag == e->h_flag, ladder))
         return ICER_FATAL_ERROR;
     HIP_TRY(hipMemcpyAsync(flag, bound_ovf, sizeof(int), hipMemcpyDeviceToHost, st));
     // the list length of each part that routed (a batch in parts: the other parts' behind the two words every caller has -- e->h_flag)
@@ -851,7 +871,8 @@ static int encode_verdict(icerx_encoder *e, int n_frames, const int *flag)
 // `regrow`: the host wrappers size the output by min(quota, slot area); when a slot-bound retry enlarges the slot area
 // they must re-allocate, signalled by *regrow (the batch is then re-run by them).
 static int encode_device_impl(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
-                              size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream, bool *regrow, bool already_begun = false)
+                              size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream, bool *regrow, bool already_begun = false,
+                              const Ladder *ladder = nullptr)
 {
     if (!e || !d_frames || !d_out || !d_sizes || !d_rcs || n_frames < 1 || n_frames > e->max_frames) {
         set_error("icerx_encode_device: invalid arguments");
@@ -868,7 +889,7 @@ static int encode_device_impl(icerx_encoder *e, const uint16_t *d_frames, int n_
         if (!begun) {
             bool rg = false;
             const int rc = encode_begin(e, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, st, e->h_flag, e->done, regrow ? &rg : nullptr,
-                                        /* overlap_ok = */ !already_begun || e->last_plan.n_parts > 1);
+                                        /* overlap_ok = */ !already_begun || e->last_plan.n_parts > 1, ladder);
             if (rc) return rc;
             if (rg) { *regrow = true; return 0; }
         }
@@ -920,6 +941,41 @@ int icerx_encoder_wait(icerx_encoder *e)
     const icerx_encoder::Pending p = e->pend;
     e->pend.active = false;
     return encode_device_impl(e, p.d_frames, p.n_frames, p.quota, p.d_out, p.out_stride, p.d_sizes, p.d_rcs, p.stream, nullptr, true);
+}
+
+// Rate ladder (include/icer_hip.h): checked here in full -- out_stride against the slot table of the largest quota -- before anything
+// is enqueued, then an ordinary synchronous call at the largest quota whose assembly cuts every quota's streams.
+int icerx_encode_device_ladder(icerx_encoder *e, const void *d_frames, int n_frames, const size_t *quotas, int n_quotas, uint8_t *d_out,
+                               size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
+{
+    if (!e || !d_frames || !quotas || !d_out || !d_sizes || !d_rcs || n_quotas < 1 || n_quotas > ICERX_MAX_LADDER || n_frames < 1 ||
+        n_frames > e->max_frames) {
+        set_error("icerx_encode_device_ladder: invalid arguments (1 <= n_quotas <= %d, 1 <= n_frames <= max_frames)", ICERX_MAX_LADDER);
+        return ICER_INVALID_INPUT;
+    }
+    if (e->pend.active) { set_error("icerx_encode_device_ladder: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
+    Ladder lq;
+    lq.n = n_quotas;
+    lq.pitch = n_frames;
+    size_t top = 0;
+    for (int q = 0; q < n_quotas; q++) { lq.quotas.q[q] = quotas[q]; top = std::max(top, quotas[q]); }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_units(e, top, st)) return ICER_FATAL_ERROR;
+    if (out_stride < top && out_stride < e->plan.slot_bytes) {
+        set_error("icerx_encode_device_ladder: out_stride %zu smaller than the largest byte quota %zu", out_stride, top);
+        return ICER_INVALID_INPUT;
+    }
+    if (n_quotas > 1 && e->final_off.ensure((size_t)n_quotas * e->max_frames * e->plan.units.size())) return ICER_FATAL_ERROR;
+    const uint16_t *planes = static_cast<const uint16_t *>(d_frames);
+    if (e->sample_bits == 8) {          // (as icerx_encode_device_s8)
+        const size_t n = (size_t)n_frames * e->channels * e->w * e->h;
+        if (e->in.ensure((size_t)e->max_frames * e->channels * e->w * e->h)) return ICER_FATAL_ERROR;
+        hipLaunchKernelGGL(widen_s8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                           static_cast<const uint8_t *>(d_frames), e->in.p, n);
+        planes = e->in.p;
+    }
+    return encode_device_impl(e, planes, n_frames, top, d_out, out_stride, d_sizes, d_rcs, stream, nullptr, false, &lq);
 }
 
 int icerx_encode_device_u8(icerx_encoder *e, const uint8_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,

@@ -5,12 +5,14 @@
 //   finalize_ll_kernel                  LL mean removal + sign-magnitude of LL (a-5, a-6; the detail bands: at the DWT store)
 //   code_units_kernel                   context modeller + entropy coder + framing (a-9..a-15)
 //   scan_kernel / gather_kernel         quota cut + final stream order (a-16, a-17)
+//   scan_ladder_kernel / gather_ladder_kernel   the same at several quotas over one coded batch (assemble_ladder.hpp)
 // HBM layout: planes are row-major int16/uint16 with row stride = image width; plane p of a batch
 // is frame-major then channel (p = frame * channels + chan).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "assemble_core.hpp"
+#include "assemble_ladder.hpp"
 #include "coder_core.hpp"
 #include "coder_wg.hpp"
 #include "coder_wg_small.hpp"
@@ -788,6 +790,42 @@ gather_kernel(const uint8_t *__restrict__ slots, size_t slot_frame_stride, const
     }
     const uint32_t done = head + body_words * 4;
     if (threadIdx.x < len - done) dst[done + threadIdx.x] = src[done + threadIdx.x];
+}
+
+// ------------------------------------------------------------------------------------------ rate ladder
+// The streams of one coded batch at several quotas (icerx_encode_device_ladder).  The output is quota-major: frame f's stream
+// at quota q is row q * pitch + f of `out` (pitch: the frames of the call; `out`, `sizes`, `rcs` of this part's first frame),
+// its final offsets are final_off[q * off_pitch + f * n_units ..].
+
+// One wavefront per (frame, quota): scan_kernel at quotas.q[q].  grid = (frames, quotas), block = 64.
+__global__ void __launch_bounds__(64)
+scan_ladder_kernel(const uint32_t *__restrict__ unit_bits, const uint32_t *__restrict__ final_order, uint32_t n_units,
+                   LadderQuotas quotas, const int *__restrict__ frame_skip, uint64_t *__restrict__ final_off, size_t off_pitch,
+                   unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs, uint32_t pitch, const UnitDesc *__restrict__ units,
+                   int *__restrict__ bound_overflow)
+{
+    const uint32_t frame = blockIdx.x, q = blockIdx.y;
+    const size_t row = (size_t)q * pitch + frame;
+    const uint32_t flags = scan_ladder_wave(unit_bits + (size_t)frame * n_units, final_order, n_units, quotas.q[q], frame_skip[frame], units,
+                                            final_off + (size_t)q * off_pitch + (size_t)frame * n_units, sizes + row, rcs + row);
+    if (flags && threadIdx.x == 0) atomicOr(bound_overflow, (int)flags);
+}
+
+// Every kept unit to its place in every quota's stream that keeps it, its slot read once.  grid = (units, frames), block = 256.
+__global__ void __launch_bounds__(256)
+gather_ladder_kernel(const uint8_t *__restrict__ slots, size_t slot_frame_stride, const UnitDesc *__restrict__ units,
+                     uint32_t n_units, const uint32_t *__restrict__ unit_bits, const uint64_t *__restrict__ final_off, size_t off_pitch,
+                     uint32_t n_q, uint8_t *__restrict__ out, size_t out_stride, uint32_t pitch)
+{
+    const uint32_t frame = blockIdx.y, ui = blockIdx.x;
+    const uint64_t *offs = final_off + (size_t)frame * n_units + ui;
+    // (a unit that no quota keeps has nothing to copy, and its bit count may be kUnitTooBig; one that some quota keeps was coded whole)
+    bool any = false;
+    for (uint32_t q = 0; q < n_q; q++) any |= offs[(size_t)q * off_pitch] != ~0ull;
+    if (!any) return;
+    const uint32_t len = kHeaderBytes + ((unit_bits[(size_t)frame * n_units + ui] + 7u) >> 3);
+    copy_unit_ladder(slots + (size_t)frame * slot_frame_stride + units[ui].slot_off, len, offs, off_pitch, n_q,
+                     out + (size_t)frame * out_stride, (size_t)pitch * out_stride, threadIdx.x, 256u);
 }
 
 }  // namespace icer

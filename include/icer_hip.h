@@ -133,6 +133,26 @@ void icerx_encoder_destroy(icerx_encoder *enc);
 int icerx_encode_device(icerx_encoder *enc, const uint16_t *d_frames, int n_frames, size_t byte_quota,
                         uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream);
 
+/* Rate ladder: the same frames at n_quotas byte quotas in one call, for about the cost of one call at the largest quota.
+ * The quota only decides where a stream is cut (DESIGN.md 3 "Rate ladder"), so the batch is transformed and coded once,
+ * planned as a call at the largest quota, and every quota's stream is cut from it.
+ *   d_frames   as icerx_encode_device takes them (uint16 planes), or as icerx_encode_device_s8 (int8 storage) for an
+ *              encoder created with sample_bits = 8; not modified
+ *   quotas     HOST array of n_quotas byte quotas, 1 <= n_quotas <= ICERX_MAX_LADDER, in any order, repeats allowed
+ *   d_out      device pointer, n_quotas * n_frames rows of out_stride bytes, quota-major: the stream of frame f at quota
+ *              quotas[q] starts at d_out + ((size_t)q * n_frames + f) * out_stride; out_stride as icerx_encode_device
+ *              requires it for the largest quota
+ *   d_sizes    device pointer, n_quotas * n_frames uint64, entry q * n_frames + f
+ *   d_rcs      device pointer, n_quotas * n_frames int32, entry q * n_frames + f
+ * Quota q's block looks exactly like one icerx_encode_device output: icerx_decode_device_async takes it with d_offsets =
+ * NULL, stream_stride = out_stride and d_lens = d_sizes + q * n_frames.  Every (f, q) has the bytes, size and return code
+ * of icerx_encode_device (or _s8) on the same frames at quotas[q].  Synchronous, with the same re-runs as
+ * icerx_encode_device.  Returns 0, ICER_INVALID_INPUT (nothing written: n_quotas or n_frames out of range, a null pointer,
+ * an asynchronous encode pending, out_stride too small) or ICER_FATAL_ERROR (HIP failure). */
+#define ICERX_MAX_LADDER 16
+int icerx_encode_device_ladder(icerx_encoder *enc, const void *d_frames, int n_frames, const size_t *quotas, int n_quotas,
+                               uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream);
+
 /* The same call in two halves.  icerx_encode_device_async returns as soon as all work is enqueued on `stream`;
  * icerx_encoder_wait returns once it has completed there (re-running the batch in the rare cases the synchronous call
  * does: a coding unit that outgrew its slot, a unit time-out).  Between the two the caller may enqueue its own copies
