@@ -33,12 +33,30 @@ def test_dropin_gray_matches_oracle(oracle, case, mode):
     assert _same(api.compress([img], st, f, sg, q), oracle.compress([img], st, f, sg, q))
 
 
-@pytest.mark.parametrize("case", [(64, 64, 2, 0, 4, 1 << 20), (128, 96, 3, 0, 10, 6000), (100, 100, 3, 2, 6, 20000),
-                                  (256, 256, 4, 1, 10, 1 << 22)])
+YUV_CASES = [(64, 64, 2, 0, 4, 1 << 20), (128, 96, 3, 0, 10, 6000), (100, 100, 3, 2, 6, 20000), (256, 256, 4, 1, 10, 1 << 22)]
+
+
+@pytest.mark.parametrize("case", YUV_CASES)
 def test_dropin_yuv_matches_oracle(oracle, case):
     w, h, st, f, sg, q = case
     planes = synth.color_frame_yuv(w, h, 3)
     assert _same(api.compress(planes, st, f, sg, q), oracle.compress(planes, st, f, sg, q))
+
+
+# the same cases against the reference build itself (oracle/_ref travels with the tree; skipped where it was not built)
+@pytest.mark.parametrize("case", GRAY_CASES)
+@pytest.mark.parametrize("mode", [0, 1])
+def test_dropin_gray_matches_reference(reference, case, mode):
+    w, h, st, f, sg, q = case
+    img = synth.gray_frame(w, h, 7, mode)
+    assert _same(api.compress([img], st, f, sg, q), reference.compress([img], st, f, sg, q))
+
+
+@pytest.mark.parametrize("case", YUV_CASES)
+def test_dropin_yuv_matches_reference(reference, case):
+    w, h, st, f, sg, q = case
+    planes = synth.color_frame_yuv(w, h, 3)
+    assert _same(api.compress(planes, st, f, sg, q), reference.compress(planes, st, f, sg, q))
 
 
 def test_dropin_matches_reference_build(reference):

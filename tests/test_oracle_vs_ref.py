@@ -108,6 +108,19 @@ SMALL_GOLDEN = ["kat_512_m1", "kat_512_m0", "kat_512_quota30000", "kat_odd_517x3
                 "u8_512_gray_full_range_overflow"]
 
 
+# the full-size rows (tests/test_gpu_fullsize.py) that the oracle reproduces in a few seconds; the 4096 x 4096 and YUV ones are left to the GPU
+FULLSIZE_SMALL_GOLDEN = ["whole_2048_filtD", "whole_2048_12bit_filtQ"]
+
+
+@pytest.mark.parametrize("name", FULLSIZE_SMALL_GOLDEN)
+def test_oracle_reproduces_fullsize_golden_vectors(oracle, golden, name):
+    g = golden[name]
+    plane = (synth.gray_frame_12bit if g["kind"] == "gray12" else synth.gray_frame)(g["w"], g["h"], g["seed"], g["mode"])
+    rc, stream, _ = oracle.compress([plane], g["stages"], g["filt"], g["segments"], g["quota"])
+    assert rc == g["rc"] and len(stream) == g["size"] and "%08x" % zlib.crc32(stream) == g["crc32"]
+    assert hashlib.sha256(stream).hexdigest()[:16] == g["sha256_16"]
+
+
 @pytest.mark.parametrize("name", SMALL_GOLDEN)
 def test_oracle_reproduces_golden_vectors(oracle, golden, name):
     """Runs everywhere (no reference needed): the committed digests came from the reference build."""
