@@ -1,0 +1,275 @@
+// recut.hpp -- icerx_recut_device_async (include/icer_hip_dec.h): stored streams ("masters") re-cut to smaller byte quotas
+// on the device, without the pixels and without re-coding.  Included by decoder.hip after decoder_async.hpp, whose blob
+// pass it reuses as it is.
+//
+//   blob       the candidate kernels of the asynchronous decode over the whole blob (mark_headers_kernel ... payload_crcs_kernel)
+//   frames     recut_plan_kernel, one workgroup per frame: the decoder's cursor walk into the frame's packet table, the
+//              units' bit counts through the recutter's unit -> table slot map (recut_core.hpp), then one wavefront per
+//              quota: the quota walk of the rate ladder (scan_ladder_wave) -> final offsets, size, return code
+//   packets    recut_gather_kernel, one workgroup per (unit, frame): the packet copied verbatim to every quota's stream
+//              that keeps it (copy_unit_recut)
+// Everything is enqueued on the caller's stream; the caller owns the workspace (recut_layout).
+#include "recut_core.hpp"
+
+#ifdef ICER_WAVE_EMU
+unsigned long long g_emu_chunks[4] = {0, 0, 0, 0};       // (coder_core.hpp's path counters of the CPU builds: unused here, defined by every emu build)
+#endif
+
+struct icerx_recutter {
+    int device = 0;
+    uint64_t w = 0, h = 0;
+    DPlanGeom geom{};
+    uint32_t n_units = 0;
+    int n_cus = 256;
+    // device tables, uploaded once: CRC-32 table, table slot of every unit and the D7 final order (Plan::units order), the
+    // unit table itself (scan_ladder_wave reads cap_is_bound of the unit at the cut: 0 here)
+    void *crc = nullptr, *unit_slot = nullptr, *final_order = nullptr, *units = nullptr;
+};
+
+namespace {
+
+#ifdef ICER_HOST_MOCK
+constexpr uint32_t kRecutPlanThreads = 1, kRecutGatherThreads = 3;    // (the mock runs a workgroup's threads one after the other)
+#else
+constexpr uint32_t kRecutPlanThreads = 256, kRecutGatherThreads = 256;
+#endif
+constexpr int kRecutMaxFrames = 65535;            // (frames are the y dimension of the gather's grid)
+
+struct RecutLayout {
+    size_t head, bitmap, gcount, scount, cands, tab_off, tab_bits, bits, foff, total;
+    uint32_t groups, supers;
+};
+
+RecutLayout recut_layout(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas)
+{
+    RecutLayout L;
+    const size_t N = (size_t)n, slots = r->geom.slots();
+    L.groups = (uint32_t)((data_bytes + kGroupBytes - 1u) / kGroupBytes);
+    L.supers = (L.groups + kSuperGroups - 1u) / kSuperGroups;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 255u) & ~(size_t)255u; return p; };
+    L.head = take(sizeof(AsyncHead));
+    L.bitmap = take(sizeof(uint32_t) * kGroupWords * (size_t)L.groups);
+    L.gcount = take(sizeof(uint32_t) * (size_t)L.groups);
+    L.scount = take(sizeof(uint32_t) * (size_t)L.supers);
+    L.cands = take(sizeof(DCandRec) * ((data_bytes + 1u) / 2u));     // (two preambles cannot overlap)
+    L.tab_off = take(sizeof(uint32_t) * N * slots);
+    L.tab_bits = take(sizeof(uint32_t) * N * slots);
+    L.bits = take(sizeof(uint32_t) * N * r->n_units);
+    L.foff = take(sizeof(uint64_t) * N * r->n_units * (size_t)n_quotas);
+    L.total = at;
+    return L;
+}
+
+// one workgroup per frame (frame k addressed as in plan_frames_kernel).  The walk: the threads summarise kPlanChunk
+// candidates into LDS, thread 0 runs the cursor rule over them and notes a valid packet of another image size; then every
+// thread reads unit bit counts out of the packet table, and wavefront v takes the quotas v, v + waves, ...: row q * n + k of
+// sizes / rcs, final offsets foff[(q * n + k) * n_units ..].
+__global__ void __launch_bounds__(256)
+recut_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uint64_t *__restrict__ offsets, uint64_t stream_stride,
+                  const uint64_t *__restrict__ lens, const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head,
+                  DPlanGeom geom, uint64_t image_w, uint64_t image_h, const uint32_t *__restrict__ unit_slot,
+                  const uint32_t *__restrict__ final_order, const UnitDesc *__restrict__ units, uint32_t n_units,
+                  LadderQuotas quotas, uint32_t n_q, uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits,
+                  uint32_t *__restrict__ unit_bits, uint64_t *__restrict__ foff, unsigned long long *__restrict__ sizes,
+                  int32_t *__restrict__ rcs)
+{
+    ICER_DYNAMIC_LDS(uint8_t, lds);                            // kPlanChunk DCand, then the walk's result
+    DCand *chunk = reinterpret_cast<DCand *>(lds);
+    DWalk *shared_walk = reinterpret_cast<DWalk *>(lds + kPlanChunk * sizeof(DCand));
+    uint32_t *shared_other = reinterpret_cast<uint32_t *>(lds + kPlanChunk * sizeof(DCand) + sizeof(DWalk));
+    const uint32_t k = blockIdx.x, n = gridDim.x, tid = threadIdx.x;
+    const uint64_t off = offsets ? offsets[k] : (uint64_t)k * stream_stride, len = lens[k];
+    const bool inside = off <= blob_len && len <= blob_len - off;
+    uint32_t *to = tab_off + (size_t)k * geom.slots(), *tb = tab_bits + (size_t)k * geom.slots();
+    uint32_t *bits = unit_bits + (size_t)k * n_units;
+    DWalk s;
+    dwalk_init(&s, image_w, image_h);
+    uint32_t other = 0;
+    if (inside) {
+        const uint32_t nc = head->n_cands, first = dlower_bound(recs, nc, (uint32_t)off), last = dlower_bound(recs, nc, (uint32_t)(off + len));
+        for (uint32_t at = first; at < last; at += kPlanChunk) {
+            const uint32_t m = last - at < kPlanChunk ? last - at : kPlanChunk;
+            for (uint32_t t = tid; t < m; t += blockDim.x) chunk[t] = dplan_summary(geom, blob, (uint32_t)off, (uint32_t)len, recs[at + t]);
+            ICER_BARRIER();
+            if (tid == 0)
+                for (uint32_t t = 0; t < m; t++) {
+                    if (chunk[t].end != 0 && chunk[t].rel >= s.cursor && (chunk[t].w != image_w || chunk[t].h != image_h)) other = 1;
+                    dplan_accept(&s, chunk[t], to, tb);
+                }
+            ICER_BARRIER();
+        }
+    }
+    if (tid == 0) { *shared_walk = s; *shared_other = other; }
+    ICER_BARRIER();
+    const int status = recut_frame_status(inside, shared_walk->cursor, *shared_other != 0u);
+    if (status == kOk) recut_unit_bits(to, tb, unit_slot, n_units, bits, tid, blockDim.x);
+    ICER_BARRIER();
+#ifdef ICER_HOST_MOCK
+    const uint32_t wave = 0, waves = 1;
+#else
+    const uint32_t wave = tid >> 6, waves = blockDim.x >> 6;
+#endif
+    for (uint32_t q = wave; q < n_q; q += waves) {
+        const size_t row = (size_t)q * n + k;
+        recut_scan_wave(status, bits, final_order, n_units, quotas.q[q], units, foff + row * n_units, sizes + row, rcs + row);
+    }
+}
+
+// one workgroup per (unit, frame): the unit's packet, wherever it lies in the master, to every quota's stream that keeps it
+__global__ void __launch_bounds__(256)
+recut_gather_kernel(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets, uint64_t stream_stride, DPlanGeom geom,
+                    const uint32_t *__restrict__ unit_slot, uint32_t n_units, const uint32_t *__restrict__ tab_off,
+                    const uint32_t *__restrict__ unit_bits, const uint64_t *__restrict__ foff, uint32_t n_q, uint8_t *__restrict__ out,
+                    size_t out_stride)
+{
+    const uint32_t ui = blockIdx.x, frame = blockIdx.y, n = gridDim.y;
+    const size_t off_pitch = (size_t)n * n_units;
+    const uint64_t *offs = foff + (size_t)frame * n_units + ui;
+    // (a frame with a status, a unit without a packet, a unit behind every cut: nothing to copy, and nothing of it is looked at)
+    bool any = false;
+    for (uint32_t q = 0; q < n_q; q++) any |= offs[(size_t)q * off_pitch] != ~0ull;
+    if (!any) return;
+    const uint64_t off = offsets ? offsets[frame] : (uint64_t)frame * stream_stride;
+    const uint32_t len = (uint32_t)kHeaderBytes + ((unit_bits[(size_t)frame * n_units + ui] + 7u) >> 3);
+    // (the walk accepted this packet: header and payload lie inside the frame, and the frame inside the blob)
+    copy_unit_recut(blob + off + tab_off[(size_t)frame * geom.slots() + unit_slot[ui]], len, offs, off_pitch, n_q,
+                    out + (size_t)frame * out_stride, (size_t)n * out_stride, threadIdx.x, blockDim.x);
+}
+
+int recut_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
+                const uint64_t *d_lens, const size_t *quotas, int n_quotas, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes,
+                int32_t *d_rcs, void *workspace, size_t workspace_bytes, hipStream_t st)
+{
+    g_error.clear();
+    if (!r || n < 1 || n > kRecutMaxFrames || n_quotas < 1 || n_quotas > kMaxLadder) return ICER_INVALID_INPUT;
+    if (!quotas || !d_lens || !d_out || !d_sizes || !d_rcs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
+    LadderQuotas lq = {};
+    size_t top = 0;
+    for (int q = 0; q < n_quotas; q++) { lq.q[q] = quotas[q]; top = std::max(top, quotas[q]); }
+    if (out_stride < top) return ICER_INVALID_INPUT;
+    if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
+    const RecutLayout L = recut_layout(r, n, data_bytes, n_quotas);
+    if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
+    int rc = ICER_RESULT_OK;
+    uint8_t *ws = (uint8_t *)workspace;
+    AsyncHead *head = (AsyncHead *)(ws + L.head);
+    DCandRec *recs = (DCandRec *)(ws + L.cands);
+    uint32_t *tab_off = (uint32_t *)(ws + L.tab_off), *tab_bits = (uint32_t *)(ws + L.tab_bits), *bits = (uint32_t *)(ws + L.bits);
+    uint64_t *foff = (uint64_t *)(ws + L.foff);
+    const uint32_t *crc_tab = (const uint32_t *)r->crc;
+    const uint32_t blob_len = (uint32_t)data_bytes;
+#ifdef ICER_HOST_MOCK
+    const uint32_t cus = kGridCus;
+#else
+    const uint32_t cus = (uint32_t)r->n_cus;
+#endif
+    auto grid = [](size_t items, size_t per_block, size_t cap) { return (unsigned)std::max<size_t>(1, std::min((items + per_block - 1) / per_block, cap)); };
+
+    // 1. candidates over the blob (decode_async's step 1)
+    HIP_TRY(hipMemsetAsync(head, 0, sizeof(AsyncHead), st));
+    HIP_TRY(hipMemsetAsync(tab_off, 0xFF, sizeof(uint32_t) * (size_t)n * r->geom.slots(), st));          // (kNoPacket)
+    if (L.groups) {
+        ICER_LAUNCH_ON(st, mark_headers_kernel, (L.groups + 255u) / 256u, 256, 0, d_data, blob_len, crc_tab, (uint32_t *)(ws + L.bitmap),
+                       (uint32_t *)(ws + L.gcount), L.groups);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, scan_groups_kernel, (L.supers + 255u) / 256u, 256, 0, (uint32_t *)(ws + L.gcount), L.groups,
+                       (uint32_t *)(ws + L.scount), L.supers);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, scan_supers_kernel, 1, 64, 0, (uint32_t *)(ws + L.scount), L.supers, head);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, compact_headers_kernel, (L.groups + 255u) / 256u, 256, 0, (const uint32_t *)(ws + L.bitmap),
+                       (const uint32_t *)(ws + L.gcount), (const uint32_t *)(ws + L.scount), L.groups, recs);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, payload_crcs_kernel, grid((data_bytes + 1u) / 2u, 4, 8u * cus), 256, 0, d_data, blob_len, crc_tab, recs, head);
+        HIP_TRY(hipGetLastError());
+    }
+    // 2. per frame: packet table, unit bit counts, the quota walk at every quota
+    ICER_LAUNCH_ON(st, recut_plan_kernel, (unsigned)n, kRecutPlanThreads, kPlanChunk * sizeof(DCand) + sizeof(DWalk) + 16u, d_data, blob_len,
+                   d_offsets, (uint64_t)stream_stride, d_lens, recs, head, r->geom, r->w, r->h, (const uint32_t *)r->unit_slot,
+                   (const uint32_t *)r->final_order, (const UnitDesc *)r->units, r->n_units, lq, (uint32_t)n_quotas, tab_off, tab_bits,
+                   bits, foff, (unsigned long long *)d_sizes, d_rcs);
+    HIP_TRY(hipGetLastError());
+    // 3. the kept packets
+    ICER_LAUNCH_ON(st, recut_gather_kernel, dim3(r->n_units, (unsigned)n), kRecutGatherThreads, 0, d_data, d_offsets, (uint64_t)stream_stride,
+                   r->geom, (const uint32_t *)r->unit_slot, r->n_units, tab_off, bits, foff, (uint32_t)n_quotas, d_out, out_stride);
+    HIP_TRY(hipGetLastError());
+done:
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+void icerx_recutter_destroy(icerx_recutter *r)
+{
+    if (!r) return;
+    for (void *p : {r->crc, r->unit_slot, r->final_order, r->units})
+        if (p) (void)hipFree(p);
+    delete r;
+}
+
+int icerx_recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments,
+                          int sample_bits)
+{
+    g_error.clear();
+    if (!out) return ICER_INVALID_INPUT;
+    *out = nullptr;
+    if (sample_bits != 8 && sample_bits != 16) return ICER_INVALID_INPUT;
+    Plan plan;
+    const int prc = build_plan(&plan, w, h, channels, stages, segments > (unsigned)kMaxSegments ? kMaxSegments + 1 : (int)segments, sample_bits);
+    if (prc != kOk) return prc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no usable HIP device");
+#ifndef ICER_HOST_MOCK
+    if (device >= 0) {
+        if (device >= ndev) return fail("device %d of %d", device, ndev);
+        if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice(%d) failed", device);
+    }
+#endif
+    icerx_recutter *r = new icerx_recutter;
+    r->device = device; r->w = w; r->h = h;
+    r->geom = DPlanGeom{(uint32_t)channels, (uint32_t)stages, segments, (uint32_t)(sample_bits == 8 ? kPlanes8 : kPlanes)};
+    r->n_units = (uint32_t)plan.units.size();
+#ifndef ICER_HOST_MOCK
+    { int cur = 0; hipDeviceProp_t prop; if (hipGetDevice(&cur) == hipSuccess && hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) r->n_cus = prop.multiProcessorCount; }
+#endif
+    uint32_t crc_tab[256];
+    build_crc32_table(crc_tab);
+    std::vector<uint32_t> slot(plan.units.size());
+    for (size_t u = 0; u < plan.units.size(); u++) {
+        const UnitDesc &d = plan.units[u];
+        slot[u] = r->geom.slot(d.chan, d.level, d.subband, d.seg, d.lsb);
+    }
+    int rc = ICER_RESULT_OK;
+    auto upload = [](void **p, const void *src, size_t bytes) {
+        const hipError_t e = hipMalloc(p, bytes);
+        return e != hipSuccess ? e : hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice);
+    };
+    HIP_TRY(upload(&r->crc, crc_tab, sizeof crc_tab));
+    HIP_TRY(upload(&r->unit_slot, slot.data(), sizeof(uint32_t) * slot.size()));
+    HIP_TRY(upload(&r->final_order, plan.final_order.data(), sizeof(uint32_t) * plan.final_order.size()));
+    HIP_TRY(upload(&r->units, plan.units.data(), sizeof(UnitDesc) * plan.units.size()));
+    *out = r;
+    return ICER_RESULT_OK;
+done:
+    icerx_recutter_destroy(r);
+    return rc;
+}
+
+size_t icerx_recut_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas)
+{
+    if (!r || n <= 0 || n_quotas < 1 || n_quotas > kMaxLadder) return 0;
+    return recut_layout(r, n, data_bytes, n_quotas).total;
+}
+
+int icerx_recut_device_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                             size_t stream_stride, const uint64_t *d_lens, const size_t *quotas, int n_quotas, uint8_t *d_out,
+                             size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return recut_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, quotas, n_quotas, d_out, out_stride,
+                       d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -194,6 +194,116 @@ class Decoder:
             raise RuntimeError(f"icerx_decode_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
 
 
+MAX_LADDER = 16                  # ICERX_MAX_LADDER
+
+
+class Recutter:
+    """Stored streams re-cut to smaller byte quotas on the device, without the pixels and without re-coding
+    (icerx_recutter_* / icerx_recut_device_async, include/icer_hip_dec.h): from a master of a frame made at quota Qm, the
+    stream the encoder makes at any quota Q <= Qm (any Q for a complete master), byte for byte.  One recutter per geometry
+    the masters were made with."""
+
+    def __init__(self, w: int, h: int, channels: int, stages: int, segments: int, bits: int = 16, device: int = -1, lib=None):
+        self.lib = lib or load_library()
+        if not hasattr(self.lib, "icerx_recut_device_async"):
+            raise RuntimeError("this build of the decoder library has no icerx_recut_device_async")
+        self.w, self.h, self.channels, self.bits = w, h, channels, bits
+        L = self.lib
+        L.icerx_recutter_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, _sz, _sz, C.c_int, C.c_int, C.c_uint, C.c_int]
+        L.icerx_recutter_destroy.argtypes = [C.c_void_p]
+        L.icerx_recutter_destroy.restype = None
+        L.icerx_recut_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, C.c_int]
+        L.icerx_recut_workspace_bytes.restype = _sz
+        L.icerx_recut_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.POINTER(_sz),
+                                               C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
+        self._workspaces = {}                # recut_torch: one cached workspace per torch stream
+        self.handle = C.c_void_p()
+        rc = L.icerx_recutter_create(C.byref(self.handle), device, w, h, channels, stages, segments, bits)
+        if rc != 0:
+            raise RuntimeError(f"icerx_recutter_create: {rc} {L.icerx_decoder_last_error().decode()}")
+
+    def close(self):
+        if self.handle:
+            self.lib.icerx_recutter_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace_bytes(self, n: int, data_bytes: int, n_quotas: int) -> int:
+        """icerx_recut_workspace_bytes: the device workspace one recut_device_async_ptrs call needs"""
+        return int(self.lib.icerx_recut_workspace_bytes(self.handle, n, data_bytes, n_quotas))
+
+    def recut_device_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, quotas,
+                                d_out: int, out_stride: int, d_sizes: int, d_rcs: int, d_workspace: int, workspace_bytes: int,
+                                stream: int = 0, n_quotas=None) -> int:
+        """icerx_recut_device_async on raw device pointers (d_offsets None: master k starts at k * stream_stride; offsets, lens,
+        sizes: uint64 / int64; rcs: int32; quotas: a host sequence, None for a null pointer).  Frame f at quota q is row
+        q * n + f of d_out and entry q * n + f of d_sizes / d_rcs.  Enqueues on `stream` and returns the call's rc without
+        waiting."""
+        arr = None if quotas is None else (_sz * max(len(quotas), 1))(*[int(q) for q in quotas])
+        nq = n_quotas if n_quotas is not None else (len(quotas) if quotas is not None else 0)
+        return self.lib.icerx_recut_device_async(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, arr, nq, d_out,
+                                                 out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, stream)
+
+    def recut_torch(self, data, lens, quotas, out, sizes, rcs, offsets=None, stream_stride=None) -> None:
+        """Re-cut n masters of a cuda uint8 tensor to every quota of `quotas` on torch's current stream, without waiting.
+
+        data: the blob, 1-D, or 2-D (n, stride) with master k in row k; lens / offsets: cuda int64 (n,), offsets None: master
+        k starts at k * stream_stride (default: data.stride(0) of a 2-D blob); out: cuda uint8 (Q, n, out_stride) or
+        (Q * n, out_stride), out_stride at least the largest quota; sizes: cuda int64 and rcs: cuda int32 of Q * n entries.
+        Row and entry q * n + f hold frame f at quotas[q], as encode_ladder leaves them, so out[q] / sizes[q] go into
+        Decoder.decode_torch as they are.  The workspace is cached per stream and grown here, on the host, before the call
+        is enqueued."""
+        import torch
+        n, Q = int(lens.shape[0]), len(quotas)
+        if offsets is None and stream_stride is None:
+            if data.dim() != 2:
+                raise ValueError("a 1-D blob needs offsets or stream_stride")
+            stream_stride = data.stride(0)
+        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8),
+                            ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32)) + \
+                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
+                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or sizes.numel() != Q * n or rcs.numel() != Q * n:
+            raise ValueError("out must be (Q * n, out_stride), sizes and rcs Q * n entries")
+        st = torch.cuda.current_stream(data.device)
+        need = self.workspace_bytes(n, data.numel(), Q)
+        work = self._workspaces.get(st.cuda_stream)
+        if work is None or work.numel() < max(need, 1):
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
+            self._workspaces[st.cuda_stream] = work
+        work.record_stream(st)
+        rc = self.recut_device_async_ptrs(n, data.data_ptr(), data.numel(), offsets.data_ptr() if offsets is not None else None,
+                                          int(stream_stride or 0), lens.data_ptr(), quotas, out.data_ptr(), out.shape[-1],
+                                          sizes.data_ptr(), rcs.data_ptr(), work.data_ptr(), work.numel(), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_recut_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+
+    def recut(self, streams, quotas):
+        """bytes in, bytes out: res[q][f] = (rc, stream) of master streams[f] re-cut to quotas[q] (copies to the device and back,
+        and waits: a convenience, not the fast path)"""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n, Q = len(streams), len(quotas)
+        lens = [len(s) for s in streams]
+        blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        stride = max(max(int(q) for q in quotas), 1)
+        out = torch.zeros((Q * n, stride), dtype=torch.uint8, device=dev)
+        sizes = torch.zeros(Q * n, dtype=torch.int64, device=dev)
+        rcs = torch.zeros(Q * n, dtype=torch.int32, device=dev)
+        self.recut_torch(torch.from_numpy(blob).to(dev), torch.tensor(lens, dtype=torch.int64, device=dev), quotas, out, sizes, rcs,
+                         offsets=torch.from_numpy(offs).to(dev))
+        torch.cuda.current_stream(dev).synchronize()
+        out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
+        return [[(int(rcs[q * n + f]), out[q * n + f, : int(sizes[q * n + f])].tobytes()) for f in range(n)] for q in range(Q)]
+
+
 # ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------
 def inverse_wavelet_transform(data: np.ndarray, filt: int, stages: int = 1, kind: str = "stages", image_w=None, image_h=None,
                               rowstride=None, N=None, stride: int = 1) -> int:

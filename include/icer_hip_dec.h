@@ -100,6 +100,56 @@ int icerx_decode_device_async(icerx_decoder *dec, int n, const void *d_data, siz
                               size_t stream_stride, const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs,
                               uint64_t *d_ws, uint64_t *d_hs, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Re-cutting stored streams to smaller byte quotas ---------------------------------------------------------------
+ * A byte quota decides only where a stream is cut, never what a packet holds.  So from a stored master stream M of a frame
+ * -- made by this project's encoders or by the reference at quota Qm, return code ICER_RESULT_OK or
+ * ICER_BYTE_QUOTA_EXCEEDED -- the stream at any quota Q <= Qm (any Q when M is complete) is cut without the pixels and
+ * without re-coding: the output has exactly the bytes, size and return code of icerx_encode_device (or _s8, or the
+ * reference) on the original frame at quota Q.  The rule: M's CRC-valid packets are found with the decoder's cursor rule
+ * (the last packet of a kind wins), each is mapped to its coding unit in priority order by (channel, level, subband, bit
+ * plane, segment), a unit without a packet counts as "does not fit", the encoder's quota walk runs at Q (a unit is kept
+ * iff its 28 header bytes fit and floor(bits / 8) < Q - used - 28; the first unit that fails ends the stream), and the
+ * kept packets are copied verbatim, header and payload, into the final stream order.
+ * Two consequences:
+ *   - Q > Qm on a cut master: the walk ends at the first unit M lacks, so the output is M itself with
+ *     ICER_BYTE_QUOTA_EXCEEDED (not what an encode at Q gives).
+ *   - a damaged master is cut at the first unit, in priority order, whose packet is missing or fails a CRC; valid packets
+ *     behind that point are dropped (the encoder's "first failure stops everything").
+ * One recutter per geometry the masters were made with; icerx_recutter_create refuses what the encoder's planner refuses,
+ * with its code (ICER_INVALID_INPUT, ICER_TOO_MANY_STAGES, ICER_TOO_MANY_SEGMENTS, ICER_PACKET_COUNT_EXCEEDED).  It uploads
+ * the unit -> packet-table slot map, the final order and the unit table once; there is no per-sample memory.
+ * device < 0: the current HIP device.  sample_bits: 16 or 8. */
+typedef struct icerx_recutter icerx_recutter;
+int icerx_recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments,
+                          int sample_bits);
+void icerx_recutter_destroy(icerx_recutter *r);
+
+/* Stream-ordered, like icerx_decode_device_async: the call only enqueues work on `stream` and returns -- no blocking copy,
+ * no synchronisation, no hipMalloc / hipFree, no host round trip.  The masters are addressed as there: master k =
+ * d_data[off_k, off_k + d_lens[k]), off_k = d_offsets[k], or k * stream_stride when d_offsets is NULL, so an encoder's d_out /
+ * out_stride / d_sizes plug in unchanged.  `quotas` is a HOST array of 1 .. ICERX_MAX_LADDER byte quotas in any order,
+ * repeats allowed, passed by value with the launch.  The outputs are laid out exactly as icerx_encode_device_ladder's:
+ * frame f at quota q is row q * n + f of d_out (out_stride bytes per row), its size and return code d_sizes[q * n + f] /
+ * d_rcs[q * n + f]; a quota's block of n rows feeds icerx_decode_device_async directly.  Per frame and quota:
+ *   every unit kept                                   ICER_RESULT_OK, the stream's length
+ *   cut                                               ICER_BYTE_QUOTA_EXCEEDED, the stream's length
+ *   the master holds no valid packet                  ICER_DECODER_OUT_OF_DATA, 0
+ *   the master leaves [0, data_bytes)                 ICER_INVALID_INPUT, 0
+ *   a valid packet's width / height are not w / h     ICER_INVALID_INPUT, 0
+ * Nothing is written behind a stream in its row, beyond the n_quotas * n rows, or to the masters.  The whole call returns
+ * ICER_INVALID_INPUT -- nothing enqueued, nothing written -- for a null pointer (d_offsets and stream excepted), n outside
+ * 1 .. 65535, n_quotas outside 1 .. ICERX_MAX_LADDER, out_stride below the largest quota or a workspace smaller than
+ * icerx_recut_workspace_bytes(r, n, data_bytes, n_quotas), and ICER_FATAL_ERROR for data_bytes past the 32-bit limit of the
+ * asynchronous decode.  The workspace (device memory, owned by the caller: about 4 bytes per blob byte for the packet
+ * candidates, a packet table per frame and 8 bytes per coding unit, frame and quota) and every buffer passed in must stay
+ * untouched until the work has completed on `stream`.  Calls on different streams may be in flight together, each with its
+ * own workspace. */
+size_t icerx_recut_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas);
+int icerx_recut_device_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                             size_t stream_stride, const uint64_t *d_lens, const size_t *quotas, int n_quotas,
+                             uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs,
+                             void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* last error message of this thread's most recent failing call ("" if none) */
 const char *icerx_decoder_last_error(void);
 
