@@ -47,7 +47,7 @@ void set_error(const char *fmt, ...)
     fprintf(stderr, "icer_hip: %s\n", buf);
 }
 
-// polite spin (the wait for a batch is tens of milliseconds; see encode_device_impl)
+// polite spin (the wait for a batch is tens of milliseconds; see wait_event)
 static inline void cpu_relax()
 {
 #if defined(__x86_64__) || defined(__i386__)
@@ -159,6 +159,30 @@ bool pin_thread_near_device(int physical)
     return sched_setaffinity(0, sizeof set, &set) == 0;
 }
 
+// The quotas of a rate ladder call (icerx_encode_device_ladder): the batch is planned and coded for the largest one, and each
+// quota's stream is cut from it (assemble_ladder.hpp).  A ladder of one quota is an ordinary call at that quota.
+struct Ladder {
+    LadderQuotas quotas;
+    int n = 0;              // quotas
+    int pitch = 0;          // frames of the call: the rows of one quota's block of the output
+};
+static_assert(kMaxLadder == ICERX_MAX_LADDER, "assemble_ladder.hpp and include/icer_hip.h agree on the ladder's length");
+
+// One encode call, as every layer between the C ABI and the kernels takes it: device pointers of its first frame, everything on `stream`.
+struct EncodeCall {
+    const uint16_t *d_frames; int n_frames; size_t quota;               // (a ladder call: its largest quota)
+    uint8_t *d_out; size_t out_stride; uint64_t *d_sizes; int32_t *d_rcs;
+    hipStream_t stream;
+    bool overlap_ok;                    // the call may be enqueued in parts on two streams (the synchronous entry points; plan_launch)
+    const Ladder *ladder = nullptr;     // a rate ladder call: the frames are cut at each of its quotas, into their rows of every quota's block.  It lives on the
+                                        // stack of icerx_encode_device_ladder, a synchronous call: a call left in icerx_encoder::Pending never has one
+    // the same call for its frames [f0, f0 + n), `frame_elems` samples each
+    EncodeCall frames(int f0, int n, size_t frame_elems) const
+    {
+        return EncodeCall{d_frames + (size_t)f0 * frame_elems, n, quota, d_out + (size_t)f0 * out_stride, out_stride, d_sizes + f0, d_rcs + f0, stream, overlap_ok, ladder};
+    }
+};
+
 }  // namespace
 
 struct icerx_encoder {
@@ -181,7 +205,7 @@ struct icerx_encoder {
     DevBuf<int16_t> coef, tmp;
     DevBuf<unsigned long long> sums;
     DevBuf<uint16_t> means;
-    DevBuf<int> flags;                  // [0,P) dwt overflow  [P,2P) mean overflow  [2P,2P+F) frame skip  [2P+F] bound overflow
+    DevBuf<int> flags;                  // status words of a batch: dwt_ovf .. bound_ovf below
     DevBuf<UnitDesc> units;
     DevBuf<uint32_t> work_order, final_order, unit_bits, done_bytes;
     DevBuf<uint64_t> final_off;
@@ -219,8 +243,7 @@ struct icerx_encoder {
     bool sleepy_wait = false;           // waits yield the core between polls (the per-device workers of a host batch) instead of spinning
     struct Pending {                    // icerx_encode_device_async .. icerx_encoder_wait
         bool active = false;
-        const uint16_t *d_frames = nullptr; int n_frames = 0; size_t quota = 0; uint8_t *d_out = nullptr; size_t out_stride = 0;
-        uint64_t *d_sizes = nullptr; int32_t *d_rcs = nullptr; void *stream = nullptr;
+        EncodeCall call = {};
     } pend;
 
     bool timing = false;
@@ -228,6 +251,15 @@ struct icerx_encoder {
     double ms[ICERX_NUM_STAGES] = {};
     uint64_t timed_calls = 0;
     bool ev_pending = false;
+
+    // `flags`, with P = max_frames * channels planes and F = max_frames frames:
+    //     [0, P) the transform left the sample range   [P, 2P) the LL mean did   [2P, 2P + F) the frame is skipped (either of the two, any channel)
+    //     [2P + F] a coding unit of the batch outgrew its slot (bit 0) or timed out (bit 1)
+    // per plane / frame from frame f0 on
+    int *dwt_ovf(int f0) const { return flags.p + (size_t)f0 * channels; }
+    int *mean_ovf(int f0) const { return flags.p + (size_t)max_frames * channels + (size_t)f0 * channels; }
+    int *skip(int f0) const { return flags.p + 2 * (size_t)max_frames * channels + f0; }
+    int *bound_ovf() const { return flags.p + 2 * (size_t)max_frames * channels + max_frames; }
 };
 
 namespace {
@@ -431,31 +463,23 @@ const char *pool_compute_level() { const char *v = getenv("ICER_HIP_COMPUTE_LEVE
 constexpr int kLonePadBytes = ICER_LONE_PAD_BYTES;      // LDS padding of the pipeline's workgroups in a split launch (launch_plan.hpp PipeKernel::Lone)
 static_assert(kUnitWavesSmall == 8 && kUnitWavesLarge == 11, "launch_plan.hpp names the pipeline's shapes by these wave counts");
 
-// The quotas of a rate ladder call (icerx_encode_device_ladder): the batch is planned and coded for the largest one, and each
-// quota's stream is cut from it (assemble_ladder.hpp).  A ladder of one quota is an ordinary call at that quota.
-struct Ladder {
-    LadderQuotas quotas;
-    int n = 0;              // quotas
-    int pitch = 0;          // frames of the call: the rows of one quota's block of the output
-};
-static_assert(kMaxLadder == ICERX_MAX_LADDER, "assemble_ladder.hpp and include/icer_hip.h agree on the ladder's length");
-
-// enqueue the whole pipeline for part `part` of the call `lp` -- the frames [f0, f0 + n_frames) of a batch -- on `st` (d_frames,
-// d_out, d_sizes, d_rcs: of frame f0); every per-frame buffer of the encoder is used from frame f0 on, so that parts of a batch can
+// enqueue the whole pipeline for part `part` of the launch `lp` -- the frames [f0, f0 + n_frames) of a batch; `c` is the call for those
+// frames, on the part's stream -- ; every per-frame buffer of the encoder is used from frame f0 on, so that parts of a batch can
 // be in flight on different streams (enqueue).  `part` also names the set of per-launch resources (route list cursor, fork / join
-// events) it takes; `timed`: it records the stage events.  `ladder` (several quotas): the part's frames are cut at each of them, into
-// their rows of every quota's block (`quota` is the largest).  Returns 0 or ICER_FATAL_ERROR.
-int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, const uint16_t *d_frames, size_t quota, uint8_t *d_out, size_t out_stride,
-                 unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool clear_bound, const Ladder *ladder = nullptr)
+// events) it takes; `timed`: it records the stage events.  Returns 0 or ICER_FATAL_ERROR.
+int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, const EncodeCall &c, bool clear_bound)
 {
     const PartPlan &pp = lp.part[part];
     const int f0 = pp.f0, n_frames = pp.n_frames;
+    const uint16_t *const d_frames = c.d_frames; uint8_t *const d_out = c.d_out; int32_t *const d_rcs = c.d_rcs;
+    unsigned long long *const d_sizes = reinterpret_cast<unsigned long long *>(c.d_sizes);
+    const size_t quota = c.quota, out_stride = c.out_stride;
+    const hipStream_t st = c.stream; const Ladder *const ladder = c.ladder;
     const bool progressive = lp.progressive, use_wg = lp.use_wg, split = pp.split, hybrid = pp.hybrid;
     const size_t W = e->w, H = e->h, plane = W * H;
     const int C = e->channels, P = n_frames * C;
     const uint32_t n_units = (uint32_t)e->plan.units.size();
-    int *dwt_ovf = e->flags.p + (size_t)f0 * C, *mean_ovf = e->flags.p + (size_t)e->max_frames * C + (size_t)f0 * C;
-    int *skip = e->flags.p + 2 * (size_t)e->max_frames * C + f0, *bound_ovf = e->flags.p + 2 * (size_t)e->max_frames * C + e->max_frames;
+    int *dwt_ovf = e->dwt_ovf(f0), *mean_ovf = e->mean_ovf(f0), *skip = e->skip(f0), *bound_ovf = e->bound_ovf();
     // this part's planes of the encoder's per-frame buffers
     int16_t *const coef = e->coef.p + (size_t)f0 * C * plane, *const tmp = e->tmp.p + (size_t)f0 * C * plane;
     unsigned long long *const sums = e->sums.p + (size_t)f0 * C;
@@ -601,26 +625,23 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
 // points is enqueued in parts on two streams -- the caller's and one of the encoder's own --, so that a part's transform and event pass
 // run beside the coder kernels of the part before it and the tail of a coder kernel (its last long units, most of the chip idle) hides
 // behind the next part's: what a caller gets from two encoders and the asynchronous calls, inside one call.  Not for
-// the asynchronous entry points (the caller overlaps whole batches itself), progressive mode, or single frames.
-int enqueue(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t quota, uint8_t *d_out, size_t out_stride,
-            unsigned long long *d_sizes, int32_t *d_rcs, hipStream_t st, bool overlap_ok, const Ladder *ladder = nullptr)
+// the asynchronous entry points (the caller overlaps whole batches itself), progressive mode, or single frames: `overlap_ok`.  A part is
+// the call for its frames (EncodeCall::frames) on its stream.
+int enqueue(icerx_encoder *e, const EncodeCall &c, bool overlap_ok)
 {
-    const int C = e->channels;
-    int *bound_ovf = e->flags.p + 2 * (size_t)e->max_frames * C + e->max_frames;
+    const hipStream_t st = c.stream;
     const CoderState cs{e->wg_available, e->wg_once, e->half_stream != nullptr};
-    const LaunchPlan &lp = e->last_plan = plan_launch(launch_shape(e), e->tuning, cs, n_frames, quota, overlap_ok);
-    if (lp.n_parts == 1) return enqueue_part(e, lp, 0, true, d_frames, quota, d_out, out_stride, d_sizes, d_rcs, st, true, ladder);
-    const size_t plane = e->w * e->h;
-    HIP_TRY(hipMemsetAsync(bound_ovf, 0, sizeof(int), st));             // (shared by the parts: before the second stream forks off)
+    const LaunchPlan &lp = e->last_plan = plan_launch(launch_shape(e), e->tuning, cs, c.n_frames, c.quota, overlap_ok);
+    if (lp.n_parts == 1) return enqueue_part(e, lp, 0, true, c, true);
+    HIP_TRY(hipMemsetAsync(e->bound_ovf(), 0, sizeof(int), st));        // (shared by the parts: before the second stream forks off)
     HIP_TRY(hipEventRecord(e->part_fork, st));                          // (the second stream starts behind whatever the caller's stream holds)
     HIP_TRY(hipStreamWaitEvent(e->half_stream, e->part_fork, 0));
     // (the stages of the parts overlap: the call's span is booked on the coder stage -- bench.py's roofline divides the call's bytes by it)
     if (e->timing) { HIP_TRY(hipEventRecord(e->ev[0], st)); HIP_TRY(hipEventRecord(e->ev[1], st)); HIP_TRY(hipEventRecord(e->ev[2], st)); }
     for (int k = 0; k < lp.n_parts; k++) {
-        const int f0 = lp.part[k].f0;
-        hipStream_t ps = (k & 1) ? e->half_stream : st;
-        if (int rc = enqueue_part(e, lp, k, false, d_frames + (size_t)f0 * C * plane, quota, d_out + (size_t)f0 * out_stride, out_stride,
-                                  d_sizes + f0, d_rcs + f0, ps, false, ladder)) return rc;
+        EncodeCall pc = c.frames(lp.part[k].f0, lp.part[k].n_frames, (size_t)e->channels * e->w * e->h);
+        pc.stream = (k & 1) ? e->half_stream : st;
+        if (int rc = enqueue_part(e, lp, k, false, pc, false)) return rc;
     }
     HIP_TRY(hipEventRecord(e->part_join, e->half_stream));
     HIP_TRY(hipStreamWaitEvent(st, e->part_join, 0));
@@ -759,6 +780,10 @@ void icerx_encoder_destroy(icerx_encoder *e)
     delete e;
 }
 
+}  // extern "C"
+
+namespace {      // the host driver of an encode call, between the entry points below and enqueue
+
 // diagnostics of a unit time-out (rare error path): which unit, which wave at which wait, and the unit's hand-off counters
 // (the record code_units_kernel leaves in the failed unit's payload slot)
 static void report_timeouts(icerx_encoder *e, int n_frames)
@@ -786,28 +811,28 @@ static void report_timeouts(icerx_encoder *e, int n_frames)
     }
 }
 
-// One encode call = begin (everything enqueued on the stream, nothing waited for) + finish (wait, then the rare re-runs).
-// `flag` = two pinned host words that receive the batch's verdict: [0] bit 0 a coding unit outgrew its provisioned slot,
-// bit 1 a unit timed out; [1] units on the route list.  `ladder`: a rate ladder call, byte_quota its largest quota.
-static int encode_begin(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
-                        size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, hipStream_t st, int *flag, hipEvent_t done, bool *regrow, bool overlap_ok = false,
-                        const Ladder *ladder = nullptr)
+// The device row that holds the longest stream a frame can have at `quota` with the current slot table (upload_units) -- the rows an entry
+// point stages for its caller, stage_rows --, and whether a caller's rows `out_stride` apart do.  A retry that enlarges the slots changes both.
+size_t row_stride(const icerx_encoder *e, size_t quota) { return std::min(quota, e->plan.slot_bytes) + 4; }
+bool stride_admissible(const icerx_encoder *e, size_t out_stride, size_t quota) { return out_stride >= quota || out_stride >= e->plan.slot_bytes; }
+
+// One encode call (EncodeCall) = encode_begin (everything enqueued on the call's stream, nothing waited for) + encode_finish (wait,
+// then the rare re-runs).  `flag` = pinned host words that receive the batch's verdict: [0] bit 0 a coding unit outgrew its
+// provisioned slot, bit 1 a unit timed out; [1] units on the route list; `done` is recorded behind them.
+int encode_begin(icerx_encoder *e, const EncodeCall &c, int *flag, hipEvent_t done)
 {
-    if (upload_units(e, byte_quota, st)) return ICER_FATAL_ERROR;
+    if (upload_units(e, c.quota, c.stream)) return ICER_FATAL_ERROR;
     if (e->slots.ensure((size_t)e->max_frames * e->plan.slot_bytes)) return ICER_FATAL_ERROR;
-    if (out_stride < byte_quota && out_stride < e->plan.slot_bytes) {
-        if (regrow) { *regrow = true; return 0; }
-        set_error("icerx_encode_device: out_stride %zu smaller than the byte quota %zu", out_stride, byte_quota);
+    if (!stride_admissible(e, c.out_stride, c.quota)) {
+        set_error("icerx_encode_device: out_stride %zu smaller than the byte quota %zu", c.out_stride, c.quota);
         return ICER_INVALID_INPUT;
     }
-    int *bound_ovf = e->flags.p + 2 * (size_t)e->max_frames * e->channels + e->max_frames;
-    if (enqueue(e, d_frames, n_frames, byte_quota, d_out, out_stride, (unsigned long long *)d_sizes, d_rcs, st, overlap_ok && flag == e->h_flag, ladder))
-        return ICER_FATAL_ERROR;
-    HIP_TRY(hipMemcpyAsync(flag, bound_ovf, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (enqueue(e, c, c.overlap_ok && flag == e->h_flag)) return ICER_FATAL_ERROR;
+    HIP_TRY(hipMemcpyAsync(flag, e->bound_ovf(), sizeof(int), hipMemcpyDeviceToHost, c.stream));
     // the list length of each part that routed (a batch in parts: the other parts' behind the two words every caller has -- e->h_flag)
     for (int k = 0; k < e->last_plan.n_parts; k++)
-        if (e->last_plan.part[k].hybrid) HIP_TRY(hipMemcpyAsync(flag + 1 + k, e->route_ctl.p + 4 * k, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(done, st));
+        if (e->last_plan.part[k].hybrid) HIP_TRY(hipMemcpyAsync(flag + 1 + k, e->route_ctl.p + 4 * k, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipEventRecord(done, c.stream));
     return 0;
 }
 
@@ -826,8 +851,8 @@ static int wait_event(hipEvent_t ev, bool sleepy)
     }
 }
 
-// The verdict of a finished batch (encode_begin's flag words): 0 = done, 1 = run it again (the encoder has been adjusted:
-// larger slots, or the barrier-only coder for the next run), or an error code.
+// The verdict of a finished batch (encode_begin's flag words), read once per run (encode_finish): 0 = done, 1 = run it again (the encoder
+// has been adjusted: larger slots at the next upload_units, or the barrier-only coder for the next run), or an error code.
 static int encode_verdict(icerx_encoder *e, int n_frames, const int *flag)
 {
     const int ovf = flag[0];
@@ -868,48 +893,93 @@ static int encode_verdict(icerx_encoder *e, int n_frames, const int *flag)
     return 1;
 }
 
-// `regrow`: the host wrappers size the output by min(quota, slot area); when a slot-bound retry enlarges the slot area
-// they must re-allocate, signalled by *regrow (the batch is then re-run by them).
-static int encode_device_impl(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
-                              size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream, bool *regrow, bool already_begun = false,
-                              const Ladder *ladder = nullptr)
+// Everything after encode_begin: wait for `done` and read the verdict; while it is "again", plan the slots anew (a no-op after a time-out),
+// let the owner of the output rows adjust them -- resize(c) may point the call at new rows; the device API passes caller_rows: its caller's
+// rows are what they are, and encode_begin refuses a stride that larger slots have made too small --, begin again and wait.
+int caller_rows(EncodeCall &) { return 0; }
+template <class Resize> int encode_finish(icerx_encoder *e, EncodeCall &c, int *flag, hipEvent_t done, Resize resize)
 {
-    if (!e || !d_frames || !d_out || !d_sizes || !d_rcs || n_frames < 1 || n_frames > e->max_frames) {
-        set_error("icerx_encode_device: invalid arguments");
-        return ICER_INVALID_INPUT;
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    hipStream_t st = (hipStream_t)stream;
-    if (!already_begun) {
-        if (e->pend.active) { set_error("icerx_encode_device: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
-        if (accumulate_timing(e)) return ICER_FATAL_ERROR;
-        e->wg_once = false;
-    }
-    for (bool begun = already_begun;; begun = false) {
-        if (!begun) {
-            bool rg = false;
-            const int rc = encode_begin(e, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, st, e->h_flag, e->done, regrow ? &rg : nullptr,
-                                        /* overlap_ok = */ !already_begun || e->last_plan.n_parts > 1, ladder);
-            if (rc) return rc;
-            if (rg) { *regrow = true; return 0; }
-        }
-        if (wait_event(e->done, e->sleepy_wait)) return ICER_FATAL_ERROR;
-        const int v = encode_verdict(e, n_frames, e->h_flag);
+    for (;;) {
+        if (wait_event(done, e->sleepy_wait)) return ICER_FATAL_ERROR;
+        const int v = encode_verdict(e, c.n_frames, flag);
         if (v < 0) return v;
         if (v == 0) break;
+        if (upload_units(e, c.quota, c.stream)) return ICER_FATAL_ERROR;
+        if (int rc = resize(c)) return rc;
+        if (int rc = encode_begin(e, c, flag, done)) return rc;
     }
     e->wg_once = false;
     return 0;
 }
 
+// The rows of the entry points that stage the streams on the device for their caller (icerx_encode_host, the lib_icer drop-ins): the
+// encoder's own `out`, a row of row_stride for each of its frames, re-made when a retry has enlarged the slots
+int stage_rows(icerx_encoder *e, EncodeCall &c)
+{
+    c.out_stride = row_stride(e, c.quota);
+    if (e->out.ensure((size_t)e->max_frames * c.out_stride)) return ICER_FATAL_ERROR;
+    c.d_out = e->out.p;
+    return 0;
+}
+
+// a synchronous call on the encoder's own flag words and event (the caller has been through enter_encode or owns the encoder)
+template <class Resize> int encode_sync(icerx_encoder *e, EncodeCall &c, Resize resize)
+{
+    if (accumulate_timing(e)) return ICER_FATAL_ERROR;
+    e->wg_once = false;
+    if (int rc = encode_begin(e, c, e->h_flag, e->done)) return rc;
+    return encode_finish(e, c, e->h_flag, e->done, resize);
+}
+int encode_staged(icerx_encoder *e, EncodeCall &c)      // ... into the encoder's own rows
+{
+    if (upload_units(e, c.quota, c.stream) || stage_rows(e, c)) return ICER_FATAL_ERROR;
+    return encode_sync(e, c, [e](EncodeCall &again) { return stage_rows(e, again); });
+}
+
+// The front door of the icerx_encode_* entry points: the arguments (`pointers`: none of the entry's is null), what the entry needs of
+// its encoder (`bits`, `channels`; 0 = any -- `needs` says it in the message), no asynchronous call pending, the device selected.
+// Returns 0, or what the entry returns (the error is set).
+const char kPendingAsync[] = "an asynchronous encode is pending on this encoder (icerx_encoder_wait)";
+int enter_encode(const char *entry, icerx_encoder *e, bool pointers, int n_frames, int bits, int channels, const char *needs, const char *pending = kPendingAsync)
+{
+    if (!e || !pointers || n_frames < 1 || n_frames > e->max_frames || (bits && e->sample_bits != bits) || (channels && e->channels != channels)) {
+        set_error("%s: invalid arguments%s", entry, needs);
+        return ICER_INVALID_INPUT;
+    }
+    if (e->pend.active) { set_error("%s: %s", entry, pending); return ICER_INVALID_INPUT; }
+    HIP_TRY(hipSetDevice(e->device));
+    return 0;
+}
+
+// Widening and narrowing between the callers' 8-bit samples and the encoder's 16-bit planes, in the encoder's staging buffers:
+// U8 8-bit gray -> uint16; S8 the uint8 twins' int8 storage -> int16; Rgb8 packed RGB888 -> Y, Cb, Cr planes (n = pixels); all from
+// `src` into e->in.  NarrowSm8: the coefficient planes (e->coef) -> int8 sign-magnitude bytes in e->in8.  n = samples of the call.
+enum class Convert { U8, S8, Rgb8, NarrowSm8 };
+int convert_samples(icerx_encoder *e, Convert how, const uint8_t *src, size_t n, hipStream_t st)
+{
+    const size_t room = (size_t)e->max_frames * e->channels * e->w * e->h;
+    if (how == Convert::NarrowSm8 ? e->in8.ensure(room) : e->in.ensure(room)) return ICER_FATAL_ERROR;
+    const dim3 grid((unsigned)std::min<size_t>((n + 255) / 256, 4096));
+    switch (how) {
+    case Convert::U8: hipLaunchKernelGGL(widen_u8_kernel, grid, dim3(256), 0, st, src, e->in.p, n); break;
+    case Convert::S8: hipLaunchKernelGGL(widen_s8_kernel, grid, dim3(256), 0, st, src, e->in.p, n); break;
+    case Convert::Rgb8: hipLaunchKernelGGL(rgb8_to_ycbcr_kernel, grid, dim3(256), 0, st, src, e->in.p, e->w * e->h, (int)(n / (e->w * e->h))); break;
+    case Convert::NarrowSm8: hipLaunchKernelGGL(narrow_sm8_kernel, grid, dim3(256), 0, st, reinterpret_cast<const uint16_t *>(e->coef.p), e->in8.p, n); break;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 int icerx_encode_device(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
                         size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
 {
-    if (e && e->sample_bits != 16) {
-        set_error("icerx_encode_device: this encoder was created for 8-bit samples (use icerx_encode_device_s8)");
-        return ICER_INVALID_INPUT;
-    }
-    return encode_device_impl(e, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, stream, nullptr);
+    if (int rc = enter_encode("icerx_encode_device", e, d_frames && d_out && d_sizes && d_rcs, n_frames, 16, 0,
+                              " (needs a 16-bit encoder; 8-bit samples: icerx_encode_device_s8)")) return rc;
+    EncodeCall c{d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, (hipStream_t)stream, true};
+    return encode_sync(e, c, caller_rows);
 }
 
 // The same call in two halves, so that a caller can overlap its own copies (or another encoder's work) with the coding:
@@ -918,19 +988,14 @@ int icerx_encode_device(icerx_encoder *e, const uint16_t *d_frames, int n_frames
 int icerx_encode_device_async(icerx_encoder *e, const uint16_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
                               size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
 {
-    if (!e || !d_frames || !d_out || !d_sizes || !d_rcs || n_frames < 1 || n_frames > e->max_frames || e->sample_bits != 16) {
-        set_error("icerx_encode_device_async: invalid arguments");
-        return ICER_INVALID_INPUT;
-    }
-    if (e->pend.active) { set_error("icerx_encode_device_async: the previous asynchronous encode has not been waited for"); return ICER_INVALID_INPUT; }
-    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = enter_encode("icerx_encode_device_async", e, d_frames && d_out && d_sizes && d_rcs, n_frames, 16, 0, "",
+                              "the previous asynchronous encode has not been waited for")) return rc;
     if (accumulate_timing(e)) return ICER_FATAL_ERROR;
     e->wg_once = false;
-    const int rc = encode_begin(e, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, (hipStream_t)stream, e->h_flag, e->done, nullptr);
-    if (rc) return rc;
+    const EncodeCall c{d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, (hipStream_t)stream, false};
+    if (int rc = encode_begin(e, c, e->h_flag, e->done)) return rc;
     e->pend.active = true;
-    e->pend.d_frames = d_frames; e->pend.n_frames = n_frames; e->pend.quota = byte_quota; e->pend.d_out = d_out; e->pend.out_stride = out_stride;
-    e->pend.d_sizes = d_sizes; e->pend.d_rcs = d_rcs; e->pend.stream = stream;
+    e->pend.call = c;
     return 0;
 }
 
@@ -938,9 +1003,9 @@ int icerx_encoder_wait(icerx_encoder *e)
 {
     if (!e) return ICER_INVALID_INPUT;
     if (!e->pend.active) return 0;
-    const icerx_encoder::Pending p = e->pend;
     e->pend.active = false;
-    return encode_device_impl(e, p.d_frames, p.n_frames, p.quota, p.d_out, p.out_stride, p.d_sizes, p.d_rcs, p.stream, nullptr, true);
+    HIP_TRY(hipSetDevice(e->device));
+    return encode_finish(e, e->pend.call, e->h_flag, e->done, caller_rows);
 }
 
 // Rate ladder (include/icer_hip.h): checked here in full -- out_stride against the slot table of the largest quota -- before anything
@@ -948,119 +1013,81 @@ int icerx_encoder_wait(icerx_encoder *e)
 int icerx_encode_device_ladder(icerx_encoder *e, const void *d_frames, int n_frames, const size_t *quotas, int n_quotas, uint8_t *d_out,
                                size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
 {
-    if (!e || !d_frames || !quotas || !d_out || !d_sizes || !d_rcs || n_quotas < 1 || n_quotas > ICERX_MAX_LADDER || n_frames < 1 ||
-        n_frames > e->max_frames) {
-        set_error("icerx_encode_device_ladder: invalid arguments (1 <= n_quotas <= %d, 1 <= n_frames <= max_frames)", ICERX_MAX_LADDER);
-        return ICER_INVALID_INPUT;
-    }
-    if (e->pend.active) { set_error("icerx_encode_device_ladder: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
+    if (int rc = enter_encode("icerx_encode_device_ladder", e, d_frames && quotas && d_out && d_sizes && d_rcs && n_quotas >= 1 && n_quotas <= ICERX_MAX_LADDER,
+                              n_frames, 0, 0, " (1 <= n_quotas <= ICERX_MAX_LADDER, 1 <= n_frames <= max_frames)")) return rc;
     Ladder lq;
     lq.n = n_quotas;
     lq.pitch = n_frames;
     size_t top = 0;
     for (int q = 0; q < n_quotas; q++) { lq.quotas.q[q] = quotas[q]; top = std::max(top, quotas[q]); }
-    HIP_TRY(hipSetDevice(e->device));
     hipStream_t st = (hipStream_t)stream;
     if (upload_units(e, top, st)) return ICER_FATAL_ERROR;
-    if (out_stride < top && out_stride < e->plan.slot_bytes) {
+    if (!stride_admissible(e, out_stride, top)) {
         set_error("icerx_encode_device_ladder: out_stride %zu smaller than the largest byte quota %zu", out_stride, top);
         return ICER_INVALID_INPUT;
     }
     if (n_quotas > 1 && e->final_off.ensure((size_t)n_quotas * e->max_frames * e->plan.units.size())) return ICER_FATAL_ERROR;
     const uint16_t *planes = static_cast<const uint16_t *>(d_frames);
     if (e->sample_bits == 8) {          // (as icerx_encode_device_s8)
-        const size_t n = (size_t)n_frames * e->channels * e->w * e->h;
-        if (e->in.ensure((size_t)e->max_frames * e->channels * e->w * e->h)) return ICER_FATAL_ERROR;
-        hipLaunchKernelGGL(widen_s8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                           static_cast<const uint8_t *>(d_frames), e->in.p, n);
+        if (convert_samples(e, Convert::S8, static_cast<const uint8_t *>(d_frames), (size_t)n_frames * e->channels * e->w * e->h, st)) return ICER_FATAL_ERROR;
         planes = e->in.p;
     }
-    return encode_device_impl(e, planes, n_frames, top, d_out, out_stride, d_sizes, d_rcs, stream, nullptr, false, &lq);
+    EncodeCall c{planes, n_frames, top, d_out, out_stride, d_sizes, d_rcs, st, true, &lq};
+    return encode_sync(e, c, caller_rows);
+}
+
+// The 8-bit front ends: converted into the encoder's own planes on `stream`, then icerx_encode_device on those.
+static int encode_converted(const char *entry, int bits, int channels, const char *needs, Convert how, icerx_encoder *e, const uint8_t *d_src, int n_frames,
+                            size_t byte_quota, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
+{
+    if (int rc = enter_encode(entry, e, d_src && d_out && d_sizes && d_rcs, n_frames, bits, channels, needs)) return rc;
+    const size_t n = (size_t)n_frames * e->w * e->h * (how == Convert::Rgb8 ? 1 : e->channels);
+    if (convert_samples(e, how, d_src, n, (hipStream_t)stream)) return ICER_FATAL_ERROR;
+    EncodeCall c{e->in.p, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, (hipStream_t)stream, true};
+    return encode_sync(e, c, caller_rows);
 }
 
 int icerx_encode_device_u8(icerx_encoder *e, const uint8_t *d_frames, int n_frames, size_t byte_quota, uint8_t *d_out,
                            size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
 {
-    if (!e || !d_frames || e->channels != 1 || n_frames < 1 || n_frames > e->max_frames) {
-        set_error("icerx_encode_device_u8: invalid arguments (needs a 1-channel encoder)");
-        return ICER_INVALID_INPUT;
-    }
-    if (e->pend.active) { set_error("icerx_encode_device_u8: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t n = (size_t)n_frames * e->w * e->h;
-    if (e->in.ensure((size_t)e->max_frames * e->w * e->h)) return ICER_FATAL_ERROR;
-    hipLaunchKernelGGL(widen_u8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       d_frames, e->in.p, n);
-    return icerx_encode_device(e, e->in.p, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, stream);
+    return encode_converted("icerx_encode_device_u8", 16, 1, " (needs a 1-channel encoder)", Convert::U8, e, d_frames, n_frames, byte_quota, d_out, out_stride,
+                            d_sizes, d_rcs, stream);
 }
 
 int icerx_encode_device_s8(icerx_encoder *e, const uint8_t *d_planes, int n_frames, size_t byte_quota, uint8_t *d_out,
                            size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
 {
-    if (!e || !d_planes || e->sample_bits != 8 || n_frames < 1 || n_frames > e->max_frames) {
-        set_error("icerx_encode_device_s8: invalid arguments (needs an encoder created with sample_bits = 8)");
-        return ICER_INVALID_INPUT;
-    }
-    if (e->pend.active) { set_error("icerx_encode_device_s8: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t n = (size_t)n_frames * e->channels * e->w * e->h;
-    if (e->in.ensure((size_t)e->max_frames * e->channels * e->w * e->h)) return ICER_FATAL_ERROR;
-    hipLaunchKernelGGL(widen_s8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream,
-                       d_planes, e->in.p, n);
-    return encode_device_impl(e, e->in.p, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, stream, nullptr);
+    return encode_converted("icerx_encode_device_s8", 8, 0, " (needs an encoder created with sample_bits = 8)", Convert::S8, e, d_planes, n_frames, byte_quota,
+                            d_out, out_stride, d_sizes, d_rcs, stream);
 }
 
 int icerx_encode_device_rgb8(icerx_encoder *e, const uint8_t *d_rgb, int n_frames, size_t byte_quota, uint8_t *d_out,
                              size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)
 {
-    if (!e || !d_rgb || e->channels != 3 || n_frames < 1 || n_frames > e->max_frames) {
-        set_error("icerx_encode_device_rgb8: invalid arguments (needs a 3-channel encoder)");
-        return ICER_INVALID_INPUT;
-    }
-    if (e->pend.active) { set_error("icerx_encode_device_rgb8: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
-    HIP_TRY(hipSetDevice(e->device));
-    const size_t npix = e->w * e->h;
-    if (e->in.ensure((size_t)e->max_frames * 3 * npix)) return ICER_FATAL_ERROR;
-    hipLaunchKernelGGL(rgb8_to_ycbcr_kernel, dim3((unsigned)std::min<size_t>((npix * n_frames + 255) / 256, 4096)), dim3(256), 0,
-                       (hipStream_t)stream, d_rgb, e->in.p, npix, n_frames);
-    return icerx_encode_device(e, e->in.p, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, stream);
+    return encode_converted("icerx_encode_device_rgb8", 16, 3, " (needs a 3-channel encoder)", Convert::Rgb8, e, d_rgb, n_frames, byte_quota, d_out, out_stride,
+                            d_sizes, d_rcs, stream);
 }
 
 int icerx_encode_host(icerx_encoder *e, const uint16_t *frames, int n_frames, size_t byte_quota, uint8_t *out,
                       size_t out_stride, uint64_t *sizes, int32_t *rcs)
 {
-    if (!e || !frames || !out || !sizes || !rcs || n_frames < 1 || n_frames > e->max_frames || e->sample_bits != 16) {
-        set_error("icerx_encode_host: invalid arguments (needs a 16-bit encoder, 1 <= n_frames <= max_frames)");
-        return ICER_INVALID_INPUT;
-    }
-    if (e->pend.active) { set_error("icerx_encode_host: an asynchronous encode is pending on this encoder (icerx_encoder_wait)"); return ICER_INVALID_INPUT; }
-    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = enter_encode("icerx_encode_host", e, frames && out && sizes && rcs, n_frames, 16, 0, " (needs a 16-bit encoder, 1 <= n_frames <= max_frames)")) return rc;
     const size_t plane = e->w * e->h, P = (size_t)n_frames * e->channels;
-    if (upload_units(e, byte_quota, nullptr)) return ICER_FATAL_ERROR;
     if (e->in.ensure((size_t)e->max_frames * e->channels * plane)) return ICER_FATAL_ERROR;
     HIP_TRY(hipMemcpy(e->in.p, frames, P * plane * 2, hipMemcpyHostToDevice));
-    for (;;) {   // the device stride depends on the slot bound, which a retry may enlarge
-        const size_t ds = byte_quota < e->plan.slot_bytes ? byte_quota : e->plan.slot_bytes;
-        if (e->out.ensure((size_t)e->max_frames * (ds + 4))) return ICER_FATAL_ERROR;
-        bool regrow = false;
-        const int rc = encode_device_impl(e, e->in.p, n_frames, byte_quota, e->out.p, ds + 4,
-                                          (uint64_t *)e->sizes.p, e->rcs.p, nullptr, &regrow);
-        if (rc) return rc;
-        if (!regrow) {
-            HIP_TRY(hipMemcpy(sizes, e->sizes.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(rcs, e->rcs.p, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
-            // out_stride is the room the caller gives every frame: checked against the streams that came out (for one
-            // frame as for many), before anything is copied
-            for (int f = 0; f < n_frames; f++)
-                if (sizes[f] > out_stride) {
-                    set_error("icerx_encode_host: stream of frame %d (%llu bytes) longer than out_stride %zu", f, (unsigned long long)sizes[f], out_stride);
-                    return ICER_OUTPUT_BUF_TOO_SMALL;
-                }
-            for (int f = 0; f < n_frames; f++)
-                if (sizes[f]) HIP_TRY(hipMemcpy(out + (size_t)f * out_stride, e->out.p + (size_t)f * (ds + 4), sizes[f], hipMemcpyDeviceToHost));
-            break;
+    EncodeCall c{e->in.p, n_frames, byte_quota, nullptr, 0, (uint64_t *)e->sizes.p, e->rcs.p, nullptr, true};       // (rows: encode_staged)
+    if (int rc = encode_staged(e, c)) return rc;
+    HIP_TRY(hipMemcpy(sizes, e->sizes.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rcs, e->rcs.p, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+    // out_stride is the room the caller gives every frame: checked against the streams that came out (for one
+    // frame as for many), before anything is copied
+    for (int f = 0; f < n_frames; f++)
+        if (sizes[f] > out_stride) {
+            set_error("icerx_encode_host: stream of frame %d (%llu bytes) longer than out_stride %zu", f, (unsigned long long)sizes[f], out_stride);
+            return ICER_OUTPUT_BUF_TOO_SMALL;
         }
-    }
+    for (int f = 0; f < n_frames; f++)
+        if (sizes[f]) HIP_TRY(hipMemcpy(out + (size_t)f * out_stride, e->out.p + (size_t)f * c.out_stride, sizes[f], hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1263,8 +1290,7 @@ int batch_prepare(BatchDevice *b, size_t w, size_t h, int channels, int stages, 
     size_t ds = 0;
     for (int k = 0; k < sets; k++) {
         if (upload_units(b->enc[k], quota, b->s_enc[k])) return ICER_FATAL_ERROR;
-        const size_t d = (quota < b->enc[k]->plan.slot_bytes ? quota : b->enc[k]->plan.slot_bytes) + 4;
-        if (d > ds) ds = d;
+        ds = std::max(ds, row_stride(b->enc[k], quota));
     }
     if (b->quota != quota || b->dev_stride < ds) {
         for (int k = 0; k < sets; k++) if (b->out[k].ensure((size_t)sub * ds)) return ICER_FATAL_ERROR;
@@ -1282,6 +1308,9 @@ int batch_run(BatchDevice *b, const uint16_t *frames, int cnt, size_t frame_elem
     std::vector<int> first, count;
     sub_batch_plan(cnt, sub, &first, &count);
     const int K = (int)first.size();
+    // sub-batch k as a call on its buffer set, and its verdict words
+    auto call_of = [&](int k) { const int s = k % S; return EncodeCall{b->in[s].p, count[(size_t)k], quota, b->out[s].p, b->dev_stride, (uint64_t *)b->d_sizes[s].p, b->d_rcs[s].p, b->s_enc[s], false}; };
+    auto flag_of = [&](int k) { return b->h_flag + 2 * (k % S); };
     // enqueue sub-batch k: its copy-in, then its kernels
     auto issue = [&](int k) -> int {
         const int s = k % S, n = count[(size_t)k];
@@ -1292,40 +1321,29 @@ int batch_run(BatchDevice *b, const uint16_t *frames, int cnt, size_t frame_elem
         HIP_TRY(hipStreamWaitEvent(b->s_enc[s], b->in_ready[s], 0));
         if (k >= S) HIP_TRY(hipStreamWaitEvent(b->s_enc[s], b->out_done[s], 0));
         b->enc[s]->wg_once = false;
-        return encode_begin(b->enc[s], b->in[s].p, n, quota, b->out[s].p, b->dev_stride, (uint64_t *)b->d_sizes[s].p, b->d_rcs[s].p, b->s_enc[s],
-                            b->h_flag + 2 * s, b->coded[s], nullptr);
+        return encode_begin(b->enc[s], call_of(k), flag_of(k), b->coded[s]);
     };
     for (int q = 0; q < S; q++) if (accumulate_timing(b->enc[q])) return ICER_FATAL_ERROR;
     for (int k = 0; k < K && k < S; k++) if ((rc = issue(k))) return rc;
     for (int k = 0; k < K; k++) {
         const int s = k % S, n = count[(size_t)k], f0 = first[(size_t)k];
         icerx_encoder *e = b->enc[s];
-        if (wait_event(b->coded[s], true)) return ICER_FATAL_ERROR;
-        int v = encode_verdict(e, n, b->h_flag + 2 * s);
-        if (v < 0) return v;
-        if (v == 1) {
-            // rare: larger slots, or the barrier-only coder after a time-out.  Let everything in flight finish (k + 1 was
-            // enqueued with the old slot table; its own verdict is read in its turn), then code k again, synchronously.
+        // rare: k is coded again, with larger slots or by the barrier-only coder after a time-out.  Let everything in flight finish first
+        // (k + 1 was enqueued with the old slot table; its own verdict is read in its turn).  Larger slots may want longer rows, of every set:
+        // the sub-batches after k that were in flight wrote rows of the old stride into buffers that are gone, so they are enqueued again.
+        auto resize = [&](EncodeCall &c) -> int {
             HIP_TRY(hipDeviceSynchronize());
-            for (;;) {
-                if (upload_units(e, quota, b->s_enc[s])) return ICER_FATAL_ERROR;
-                if (e->slots.ensure((size_t)e->max_frames * e->plan.slot_bytes)) return ICER_FATAL_ERROR;
-                const size_t ds = (quota < e->plan.slot_bytes ? quota : e->plan.slot_bytes) + 4;
-                if (b->dev_stride < ds) {
-                    for (int q = 0; q < S; q++) if (b->out[q].ensure((size_t)sub * ds)) return ICER_FATAL_ERROR;
-                    b->dev_stride = ds;
-                    // (the sub-batches after k that were in flight wrote rows of the old stride into buffers that are gone: enqueue them again)
-                    for (int q = k + 1; q < K && q < k + S; q++) if ((rc = issue(q))) return rc;
-                }
-                if ((rc = encode_begin(e, b->in[s].p, n, quota, b->out[s].p, b->dev_stride, (uint64_t *)b->d_sizes[s].p, b->d_rcs[s].p, b->s_enc[s],
-                                       b->h_flag + 2 * s, b->coded[s], nullptr))) return rc;
-                if (wait_event(b->coded[s], true)) return ICER_FATAL_ERROR;
-                v = encode_verdict(e, n, b->h_flag + 2 * s);
-                if (v < 0) return v;
-                if (v == 0) break;
+            const size_t ds = row_stride(e, quota);
+            if (b->dev_stride < ds) {
+                for (int q = 0; q < S; q++) if (b->out[q].ensure((size_t)sub * ds)) return ICER_FATAL_ERROR;
+                b->dev_stride = ds;
+                for (int q = k + 1; q < K && q < k + S; q++) if (int r = issue(q)) return r;
             }
-            e->wg_once = false;
-        }
+            c = call_of(k);
+            return 0;
+        };
+        EncodeCall c = call_of(k);
+        if ((rc = encode_finish(e, c, flag_of(k), b->coded[s], resize))) return rc;
         // lengths and return codes of k, then exactly the bytes of every stream
         HIP_TRY(hipStreamWaitEvent(b->s_out, b->coded[s], 0));
         HIP_TRY(hipMemcpyAsync(b->h_sizes + (size_t)s * sub, b->d_sizes[s].p, (size_t)n * 8, hipMemcpyDeviceToHost, b->s_out));
@@ -1597,15 +1615,10 @@ static int compress_planes(void *const planes[], int channels, size_t w, size_t 
                                                            : hipMemcpy(t->in.p + (size_t)c * plane, planes[c], plane * 2, hipMemcpyHostToDevice);
                     if (he != hipSuccess) r = ICER_FATAL_ERROR;
                 }
+                if (!r && sample_bits == 8) r = convert_samples(t, Convert::S8, t->in8.p, n, nullptr);
                 if (!r) {
-                    if (sample_bits == 8)
-                        hipLaunchKernelGGL(widen_s8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, nullptr, t->in8.p, t->in.p, n);
-                    for (;;) {
-                        if (upload_units(t, 64, nullptr) || t->out.ensure((size_t)channels * 128)) { r = ICER_FATAL_ERROR; break; }
-                        bool regrow = false;
-                        r = encode_device_impl(t, t->in.p, channels, 64, t->out.p, 128, (uint64_t *)t->sizes.p, t->rcs.p, nullptr, &regrow);
-                        if (r || !regrow) break;
-                    }
+                    EncodeCall c{t->in.p, channels, 64, nullptr, 0, (uint64_t *)t->sizes.p, t->rcs.p, nullptr, true};
+                    r = encode_staged(t, c);
                     if (!r && hipMemcpy(rcs.data(), t->rcs.p, sizeof(int32_t) * channels, hipMemcpyDeviceToHost) != hipSuccess) r = ICER_FATAL_ERROR;
                 }
                 icerx_encoder_destroy(t);
@@ -1634,51 +1647,38 @@ static int compress_planes(void *const planes[], int channels, size_t w, size_t 
         if (e->in8.ensure((size_t)channels * plane)) return ICER_FATAL_ERROR;
         for (int c = 0; c < channels; c++)
             HIP_TRY(hipMemcpyAsync(e->in8.p + (size_t)c * plane, planes[c], plane, hipMemcpyHostToDevice, st));
-        const size_t n = (size_t)channels * plane;
-        hipLaunchKernelGGL(widen_s8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st, e->in8.p, e->in.p, n);
+        if (convert_samples(e, Convert::S8, e->in8.p, (size_t)channels * plane, st)) return ICER_FATAL_ERROR;
     }
     uint64_t size = 0;
     int32_t rc = 0;
     bool coef_back = false;              // the coefficient planes are in the caller's image already
-    for (bool first = true;; first = false) {
-        if (upload_units(e, quota, st)) return ICER_FATAL_ERROR;
-        const size_t ds = (quota < e->plan.slot_bytes ? quota : e->plan.slot_bytes) + 4;
-        if (e->out.ensure(ds)) return ICER_FATAL_ERROR;
-        bool regrow = false;
-        int r;
-        if (first) {
-            if (accumulate_timing(e)) return ICER_FATAL_ERROR;
-            e->wg_once = false;
-            r = encode_begin(e, e->in.p, 1, quota, e->out.p, ds, (uint64_t *)e->sizes.p, e->rcs.p, st, e->h_flag, e->done, nullptr);
-            if (r) return r;
-            // beside the coder: the frame's status (an aborted frame keeps the caller's planes, see below), then the planes
-            int skip = 0;
-            const int *d_skip = e->flags.p + 2 * (size_t)e->max_frames * channels;
-            HIP_TRY(hipStreamWaitEvent(e->copy_stream, e->coef_ready, 0));
-            HIP_TRY(hipMemcpyAsync(&skip, d_skip, sizeof(int), hipMemcpyDeviceToHost, e->copy_stream));
-            HIP_TRY(hipStreamSynchronize(e->copy_stream));
-            if (!skip) {
-                if (sample_bits == 16) {
-                    for (int c = 0; c < channels; c++)
-                        HIP_TRY(hipMemcpyAsync(planes[c], e->coef.p + (size_t)c * plane, plane * 2, hipMemcpyDeviceToHost, e->copy_stream));
-                } else {
-                    // what the reference leaves in the caller's image: int8 sign-magnitude bytes; narrowed on the device (in8 is
-                    // free again: the widening kernel has run, coef_ready lies behind it on the encode stream)
-                    const size_t n = (size_t)channels * plane;
-                    hipLaunchKernelGGL(narrow_sm8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, e->copy_stream,
-                                       reinterpret_cast<const uint16_t *>(e->coef.p), e->in8.p, n);
-                    for (int c = 0; c < channels; c++)
-                        HIP_TRY(hipMemcpyAsync(planes[c], e->in8.p + (size_t)c * plane, plane, hipMemcpyDeviceToHost, e->copy_stream));
-                }
-                HIP_TRY(hipStreamSynchronize(e->copy_stream));
-                coef_back = true;
+    // begin, copy the coefficients back beside the coder, finish
+    EncodeCall call{e->in.p, 1, quota, nullptr, 0, (uint64_t *)e->sizes.p, e->rcs.p, st, false};
+    if (upload_units(e, quota, st) || stage_rows(e, call)) return ICER_FATAL_ERROR;
+    if (accumulate_timing(e)) return ICER_FATAL_ERROR;
+    e->wg_once = false;
+    if (int r = encode_begin(e, call, e->h_flag, e->done)) return r;
+    {   // beside the coder: the frame's status (an aborted frame keeps the caller's planes, see below), then the planes
+        int skip = 0;
+        HIP_TRY(hipStreamWaitEvent(e->copy_stream, e->coef_ready, 0));
+        HIP_TRY(hipMemcpyAsync(&skip, e->skip(0), sizeof(int), hipMemcpyDeviceToHost, e->copy_stream));
+        HIP_TRY(hipStreamSynchronize(e->copy_stream));
+        if (!skip) {
+            if (sample_bits == 16) {
+                for (int c = 0; c < channels; c++)
+                    HIP_TRY(hipMemcpyAsync(planes[c], e->coef.p + (size_t)c * plane, plane * 2, hipMemcpyDeviceToHost, e->copy_stream));
+            } else {
+                // what the reference leaves in the caller's image: int8 sign-magnitude bytes; narrowed on the device (in8 is
+                // free again: the widening kernel has run, coef_ready lies behind it on the encode stream)
+                if (convert_samples(e, Convert::NarrowSm8, nullptr, (size_t)channels * plane, e->copy_stream)) return ICER_FATAL_ERROR;
+                for (int c = 0; c < channels; c++)
+                    HIP_TRY(hipMemcpyAsync(planes[c], e->in8.p + (size_t)c * plane, plane, hipMemcpyDeviceToHost, e->copy_stream));
             }
-            r = encode_device_impl(e, e->in.p, 1, quota, e->out.p, ds, (uint64_t *)e->sizes.p, e->rcs.p, st, &regrow, true);
-        } else
-            r = encode_device_impl(e, e->in.p, 1, quota, e->out.p, ds, (uint64_t *)e->sizes.p, e->rcs.p, st, &regrow);
-        if (r) return r;
-        if (!regrow) break;
+            HIP_TRY(hipStreamSynchronize(e->copy_stream));
+            coef_back = true;
+        }
     }
+    if (int r = encode_finish(e, call, e->h_flag, e->done, [e](EncodeCall &again) { return stage_rows(e, again); })) return r;
     HIP_TRY(hipMemcpyAsync(&size, e->sizes.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&rc, e->rcs.p, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1689,14 +1689,13 @@ static int compress_planes(void *const planes[], int channels, size_t w, size_t 
         // truncating int8 stores after the overflow; we leave the caller's planes untouched instead.)
         if (sample_bits == 8) return rc;
         std::vector<int> fl(2 * (size_t)channels);
-        HIP_TRY(hipMemcpy(fl.data(), e->flags.p, sizeof(int) * channels, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(fl.data(), e->dwt_ovf(0), sizeof(int) * channels, hipMemcpyDeviceToHost));
         int last = channels - 1;
         for (int c = 0; c < channels; c++) if (fl[c]) { last = c; break; }
         // (the detail bands are normally stored as sign-magnitude words: transform once more, plain)
         {
             size_t cw2 = w, ch2 = h;
-            int *scratch_flags = e->flags.p;
-            launch_dwt(e, reinterpret_cast<const uint16_t *>(e->in.p), 1, st, 0, scratch_flags, &cw2, &ch2);
+            launch_dwt(e, reinterpret_cast<const uint16_t *>(e->in.p), 1, st, 0, /* scratch */ e->dwt_ovf(0), &cw2, &ch2);
             HIP_TRY(hipStreamSynchronize(st));
         }
         for (int c = 0; c <= last; c++)
@@ -1710,9 +1709,7 @@ static int compress_planes(void *const planes[], int channels, size_t w, size_t 
             for (int c = 0; c < channels; c++)
                 HIP_TRY(hipMemcpy(planes[c], e->coef.p + (size_t)c * plane, plane * 2, hipMemcpyDeviceToHost));
         } else {
-            const size_t n = (size_t)channels * plane;
-            hipLaunchKernelGGL(narrow_sm8_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                               reinterpret_cast<const uint16_t *>(e->coef.p), e->in8.p, n);
+            if (convert_samples(e, Convert::NarrowSm8, nullptr, (size_t)channels * plane, st)) return ICER_FATAL_ERROR;
             for (int c = 0; c < channels; c++)
                 HIP_TRY(hipMemcpyAsync(planes[c], e->in8.p + (size_t)c * plane, plane, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));

@@ -5,6 +5,12 @@ lists that are full or empty, and seeded sequences of calls on long-lived encode
 change from call to call.  Every call also checks the promises of include/icer_hip.h about the caller's buffers: d_frames is
 not modified, nothing is written beyond the n_frames rows of d_out / entries of d_sizes and d_rcs, nor behind a frame's stream
 within its row."""
+import json
+import os
+import subprocess
+import sys
+import zlib
+
 import numpy as np
 import pytest
 
@@ -13,6 +19,7 @@ from tests import encoder_batch_cases as ebc
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENT, SENT_SIZE, SENT_RC = 0xA5, 0x5A5A5A5A5A5A5A5A, -777
 FRONT_ENDS = {"u8": "icerx_encode_device_u8", "rgb8": "icerx_encode_device_rgb8", "s8": "icerx_encode_device_s8"}
 
@@ -264,21 +271,45 @@ def test_long_lived_encoder_sequence(expected, monkeypatch, name):
 
 
 # ---- slot retries in the middle of a sequence ---------------------------------------------------------------------------------
+RETRY = ebc.Geometry(256, 256, 1, 1, 0, 1)
+RETRY_SPECS = [("blank", 0), ("flat", 0), ("noise8", 0), ("dot", 0)]
+
+
+def slot_area_at_1bpp(emu, g):
+    """the slot area of a frame provisioned at 1 bit per sample when no unit is capped by the quota (plan.hpp assign_slots: per unit a
+    28-byte header and (samples + 31) / 32 + 16 words): the most ICER_HIP_SLOT_BPP=1 can provision before the first retry"""
+    _, units = emu.plan_units(g.w, g.h, g.channels, g.stages, g.segments)
+    npix = units[:, 2].astype(np.int64) * units[:, 3]
+    return int(np.sum(28 + 4 * ((npix + 31) // 32 + 16)))
+
+
+def retry_quota(emu, g):
+    """a quota above the slot area at 1 bit per sample: the rows an entry point stages for itself are min(quota, slot area) + 4 bytes
+    long, so they depend on the slot table and must grow when a retry enlarges it"""
+    q = ebc.quota(g, "lossless")
+    if q <= slot_area_at_1bpp(emu, g):
+        q = 2 * g.w * g.h
+    assert q > slot_area_at_1bpp(emu, g)
+    return q
+
+
 @pytest.mark.timeout(300)
-@pytest.mark.parametrize("entry", ["sync", "async"])
-def test_slot_retry_mid_sequence(expected, monkeypatch, entry):
+@pytest.mark.parametrize("entry", ["sync", "async", "host"])
+def test_slot_retry_mid_sequence(expected, emu, monkeypatch, entry):
     """slots provisioned at 1 bit per sample (ICER_HIP_SLOT_BPP, read at create): in a mixed batch only the noise frame outgrows
-    its slots and the batch is run again with larger ones (asynchronous: inside the wait); the calls after it, at other quotas,
-    rebuild the slot table at the doubled bound.  Every stream stays exact."""
+    its slots and the batch is run again with larger ones (asynchronous: inside the wait; host: with longer staging rows, the quota
+    being above the first slot area); the calls after it, at other quotas, rebuild the slot table at the doubled bound.  Every
+    stream stays exact."""
     monkeypatch.setenv("ICER_HIP_SLOT_BPP", "1")
-    g = ebc.Geometry(256, 256, 1, 1, 0, 1)
+    g, specs = RETRY, RETRY_SPECS
     enc = api.Encoder(g.w, g.h, 1, g.stages, g.filt, g.segments, max_frames=4)
     assert enc.info()["slot_bits_per_pixel"] == 1
-    specs = [("blank", 0), ("flat", 0), ("noise8", 0), ("dot", 0)]
-    q = ebc.quota(g, "lossless")
+    q = retry_quota(emu, g)
+    assert q > enc.info()["slot_bytes_per_frame"], (q, enc.info())     # (and above what the first call will plan: retry_quota)
     check(expected, g, specs, q, encode(enc, g, entry, ebc.batch(g, specs), q), f"{entry} retry", enc)
     retries = enc.stats()["slot_retries"]
     assert retries >= 1 and enc.info()["slot_bits_per_pixel"] > 1, (enc.stats(), enc.info())
+    assert enc.info()["slot_bytes_per_frame"] > slot_area_at_1bpp(emu, g)      # (the staged rows of the first run were too short for the second)
     for cls in ("cut", "progressive", "tiny60", "lossless"):
         q = ebc.quota(g, cls)
         for order in (specs, specs[::-1], specs[:2]):
@@ -286,3 +317,68 @@ def test_slot_retry_mid_sequence(expected, monkeypatch, entry):
     assert enc.info()["slot_bits_per_pixel"] > 1
     assert enc.stats()["slot_retries"] == retries and enc.stats()["unit_timeouts"] == 0, enc.stats()
     enc.close()
+
+
+def run_child(code, tmp_path, **env):
+    """`code` in a process of its own (the pooled encoders of the host batch and of the lib_icer entry points read the environment when
+    they are created, and live as long as the process); returns the JSON object of its last line of output"""
+    prologue = f"import json, sys, zlib\nimport numpy as np\nsys.path.insert(0, {ROOT!r})\nfrom icer_compression_amd import api\ntmp = {str(tmp_path)!r}\n"
+    r = subprocess.run([sys.executable, "-c", prologue + code], capture_output=True, text=True, timeout=240, env=dict(os.environ, **env))
+    assert r.returncode == 0, r.stdout + r.stderr
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.timeout(300)
+def test_slot_retry_inside_the_host_batch_pipeline(expected, emu, tmp_path):
+    """icerx_compress_batch_uint16_devices in sub-batches of two: the noise frame of sub-batch 0 outgrows its slots while sub-batch 1 is
+    in flight with rows of the old stride; the pipeline re-allocates its rows, codes sub-batch 0 again and issues sub-batch 1 again.
+    A second call of the same process, at another quota, runs on the grown slots without a retry."""
+    g = RETRY
+    specs = [RETRY_SPECS[0], RETRY_SPECS[2], RETRY_SPECS[1], RETRY_SPECS[3]]        # (blank, noise8 | flat, dot)
+    quotas = [retry_quota(emu, g), ebc.quota(g, "cut")]
+    np.save(tmp_path / "frames.npy", ebc.batch(g, specs))
+    got = run_child(f"""
+frames = np.load(tmp + "/frames.npy")
+n, calls = frames.shape[0], []
+for q in {quotas!r}:
+    out = np.zeros((n, q + 5), np.uint8); sizes = np.zeros(n, np.uint64); rcs = np.zeros(n, np.int32)
+    rc = api.compress_batch(frames, {g.stages}, {g.filt}, {g.segments}, q, out, sizes, rcs, devices=[0])
+    calls.append({{"rc": rc, "rcs": rcs.tolist(), "sizes": sizes.tolist(), "crc": [zlib.crc32(out[k, :int(sizes[k])].tobytes()) for k in range(n)],
+                  "stats": api.process_stats()}})
+print(json.dumps(calls))
+""", tmp_path, ICER_HIP_SLOT_BPP="1", ICER_HIP_BATCH_SUB="2")
+    for q, call in zip(quotas, got):
+        assert call["rc"] == 0, call
+        for k, spec in enumerate(specs):
+            rc, stream = expected(g, spec, q)[:2]
+            assert (call["rcs"][k], call["sizes"][k], call["crc"][k]) == (rc, len(stream), zlib.crc32(stream)), (q, k, spec)
+        assert call["stats"]["unit_timeouts"] == 0, call["stats"]
+    assert got[0]["stats"]["slot_retries"] >= 1 and got[1]["stats"]["slot_retries"] == got[0]["stats"]["slot_retries"], [c["stats"] for c in got]
+
+
+@pytest.mark.timeout(300)
+def test_slot_retry_inside_the_drop_in_call(expected, emu, tmp_path):
+    """icer_compress_image_uint16 on a noise image with slots at 1 bit per sample: the cached encoder runs the image again with larger
+    slots and a longer staging row; the stream and the coefficient plane left in the caller's image are the oracle's.  A second image
+    in the same process is coded on the grown slots without a retry."""
+    g = RETRY
+    specs = [("noise8", 0), ("noise8", 1)]
+    q = retry_quota(emu, g)
+    np.save(tmp_path / "frames.npy", ebc.batch(g, specs))
+    got = run_child(f"""
+frames = np.load(tmp + "/frames.npy")
+calls = []
+for k in range(frames.shape[0]):
+    rc, stream, planes = api.compress(list(frames[k]), {g.stages}, {g.filt}, {g.segments}, {q})
+    np.save(tmp + f"/planes{{k}}.npy", np.stack(planes))
+    with open(tmp + f"/stream{{k}}.bin", "wb") as fh:
+        fh.write(stream)
+    calls.append({{"rc": rc, "stats": api.process_stats()}})
+print(json.dumps(calls))
+""", tmp_path, ICER_HIP_SLOT_BPP="1")
+    for k, spec in enumerate(specs):
+        want = expected(g, spec, q)
+        ebc.check_frame(got[k]["rc"], (tmp_path / f"stream{k}.bin").read_bytes(), want, f"drop-in call {k} {spec}")
+        ebc.check_coefficients(g, list(np.load(tmp_path / f"planes{k}.npy")), want, f"drop-in call {k} {spec}")
+        assert got[k]["stats"]["unit_timeouts"] == 0, got[k]["stats"]
+    assert got[0]["stats"]["slot_retries"] >= 1 and got[1]["stats"]["slot_retries"] == got[0]["stats"]["slot_retries"], [c["stats"] for c in got]
