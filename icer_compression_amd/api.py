@@ -81,6 +81,11 @@ def load_library() -> C.CDLL:
     L.icerx_encode_device_async.argtypes = L.icerx_encode_device.argtypes
     L.icerx_encode_device_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icerx_encode_device_target.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icerx_target_threshold.restype = C.c_uint64
+    L.icerx_target_threshold.argtypes = [C.c_void_p, C.c_double]
+    L.icerx_get_distortion_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     L.icerx_encoder_wait.argtypes = [C.c_void_p]
     L.icerx_compress_batch_uint16.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
@@ -270,6 +275,48 @@ class Encoder:
         st = torch.cuda.current_stream(dev).cuda_stream
         self.encode_ladder_ptrs(frames.data_ptr(), n, quotas, out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(), st)
         return out, sizes, rcs
+
+    def encode_target_ptrs(self, d_frames: int, n_frames: int, targets_mse, byte_cap: int, d_out: int, out_stride: int, d_sizes: int,
+                           d_rcs: int, d_reached: int, d_dist: int, d_equiv_quota: int, stream: int = 0) -> None:
+        """icerx_encode_device_target: every frame cut where each mean-squared-error target of `targets_mse` (at most
+        ICERX_MAX_LADDER) is met, or at byte_cap; frame f at targets_mse[t] goes to row / entry t * n_frames + f of the outputs"""
+        ts = [float(t) for t in targets_mse]
+        arr = (C.c_double * max(len(ts), 1))(*ts)
+        rc = self.lib.icerx_encode_device_target(self.handle, d_frames, n_frames, arr, len(ts), byte_cap, d_out, out_stride, d_sizes, d_rcs,
+                                                 d_reached, d_dist, d_equiv_quota, stream)
+        if rc != 0:
+            raise IcerHipError(f"icerx_encode_device_target rc={rc}: {self.lib.icerx_last_error().decode()}")
+
+    def encode_target_torch(self, frames, targets, byte_cap: int, psnr: bool = False):
+        """frames: as encode_ladder_torch takes them.  targets: mean squared errors per sample, or with psnr=True peak
+        signal-to-noise ratios in dB against the encoder's sample peak (2^sample_bits - 1), converted on the host.  Returns cuda
+        tensors (out uint8 (T, n, byte_cap), sizes int64 (T, n), rcs int32 (T, n), reached int32 (T, n), dist int64 (T, n) holding
+        the uint64 distortions, equiv_quota int64 (T, n)), on torch's current stream."""
+        import torch
+        peak = float((1 << self.sample_bits) - 1)
+        mse = [peak * peak / 10.0 ** (float(t) / 10.0) for t in targets] if psnr else [float(t) for t in targets]
+        n, T, dev = frames.shape[0], len(mse), frames.device
+        out = torch.empty((T, n, int(byte_cap)), dtype=torch.uint8, device=dev)
+        sizes, dist, equiv = (torch.empty((T, n), dtype=torch.int64, device=dev) for _ in range(3))
+        rcs, reached = (torch.empty((T, n), dtype=torch.int32, device=dev) for _ in range(2))
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.encode_target_ptrs(frames.data_ptr(), n, mse, int(byte_cap), out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(),
+                                reached.data_ptr(), dist.data_ptr(), equiv.data_ptr(), st)
+        return out, sizes, rcs, reached, dist, equiv
+
+    def target_threshold(self, target_mse: float) -> int:
+        """the integer threshold a target becomes (icerx_target_threshold): floor(target_mse * samples * 16)"""
+        return int(self.lib.icerx_target_threshold(self.handle, float(target_mse)))
+
+    def distortion_table(self, frame: int = 0) -> np.ndarray:
+        """the families' residual energies of `frame` in the last target call (icerx_get_distortion_table): uint64 (families, P + 1)"""
+        planes = 7 if self.sample_bits == 8 else 9
+        families = self.info()["units_per_frame"] // planes          # (a family = the coded planes of one rectangle, csrc/plan.hpp)
+        dst = np.zeros((families, planes + 1), np.uint64)
+        rc = self.lib.icerx_get_distortion_table(self.handle, frame, dst.ctypes.data, dst.size)
+        if rc != 0:
+            raise IcerHipError(f"icerx_get_distortion_table rc={rc}: no target call yet, or the frame was not part of the last one")
+        return dst
 
     def encode_torch_s8(self, planes, byte_quota: int):
         """uint8 twins: planes = cuda uint8 tensor (n, h, w) or (n, channels, h, w), int8 storage; the encoder must have

@@ -22,6 +22,7 @@
 #include "../../include/icer_hip.h"
 #include "kernels.hpp"
 #include "launch_plan.hpp"
+#include "subband_gain.hpp"
 
 using namespace icer;
 
@@ -168,6 +169,16 @@ struct Ladder {
 };
 static_assert(kMaxLadder == ICERX_MAX_LADDER, "assemble_ladder.hpp and include/icer_hip.h agree on the ladder's length");
 
+// The targets of a quality-targeted call (icerx_encode_device_target): the batch is planned and coded as a call at the byte cap, and
+// each target's stream is cut from it where the target is met (distortion_core.hpp).  Output rows are target-major, as a ladder's.
+struct Target {
+    TargetList thresholds;
+    int n = 0;              // targets
+    int pitch = 0;          // frames of the call
+    int32_t *d_reached = nullptr;                   // per (target, frame), of the call's first frame
+    unsigned long long *d_dist = nullptr, *d_equiv = nullptr;
+};
+
 // One encode call, as every layer between the C ABI and the kernels takes it: device pointers of its first frame, everything on `stream`.
 struct EncodeCall {
     const uint16_t *d_frames; int n_frames; size_t quota;               // (a ladder call: its largest quota)
@@ -176,10 +187,11 @@ struct EncodeCall {
     bool overlap_ok;                    // the call may be enqueued in parts on two streams (the synchronous entry points; plan_launch)
     const Ladder *ladder = nullptr;     // a rate ladder call: the frames are cut at each of its quotas, into their rows of every quota's block.  It lives on the
                                         // stack of icerx_encode_device_ladder, a synchronous call: a call left in icerx_encoder::Pending never has one
+    const Target *target = nullptr;     // a quality-targeted call (quota = its byte cap): the same, on the stack of icerx_encode_device_target
     // the same call for its frames [f0, f0 + n), `frame_elems` samples each
     EncodeCall frames(int f0, int n, size_t frame_elems) const
     {
-        return EncodeCall{d_frames + (size_t)f0 * frame_elems, n, quota, d_out + (size_t)f0 * out_stride, out_stride, d_sizes + f0, d_rcs + f0, stream, overlap_ok, ladder};
+        return EncodeCall{d_frames + (size_t)f0 * frame_elems, n, quota, d_out + (size_t)f0 * out_stride, out_stride, d_sizes + f0, d_rcs + f0, stream, overlap_ok, ladder, target};
     }
 };
 
@@ -236,6 +248,13 @@ struct icerx_encoder {
     DevBuf<unsigned long long> sizes;
     DevBuf<int32_t> rcs;
     DevBuf<uint64_t> prof;              // profiling build only (-DICER_PHASE_TIMERS): per-phase cycle sums
+    // quality-targeted calls (distortion_core.hpp): made by the first icerx_encode_device_target, nothing before
+    DevBuf<unsigned long long> dist;    // E[max_frames][plan.n_families][planes + 1]: the families' residual energies of the last target call
+    DevBuf<uint32_t> fam_weight;        // the subband weight of each family (subband_gain.hpp)
+    DevBuf<uint32_t> fam_chan;          // its channel
+    DevBuf<unsigned long long> fam_ll_term;   // weight x coefficients of an LL family of a 16-bit encoder, else 0 (distortion_core.hpp mean_loss)
+    hipEvent_t energy_fork[kMaxParts] = {}, energy_join[kMaxParts] = {};   // per part: the energy pass on the side stream
+    int dist_frames = 0;                // frames of the last target call (icerx_get_distortion_table)
 
     int *h_flag = nullptr;              // pinned host words: slot-bound overflow flag of the last batch, units on its route list
     hipEvent_t done = nullptr;          // end of the last batch on its stream
@@ -474,7 +493,7 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
     const uint16_t *const d_frames = c.d_frames; uint8_t *const d_out = c.d_out; int32_t *const d_rcs = c.d_rcs;
     unsigned long long *const d_sizes = reinterpret_cast<unsigned long long *>(c.d_sizes);
     const size_t quota = c.quota, out_stride = c.out_stride;
-    const hipStream_t st = c.stream; const Ladder *const ladder = c.ladder;
+    const hipStream_t st = c.stream; const Ladder *const ladder = c.ladder; const Target *const target = c.target;
     const bool progressive = lp.progressive, use_wg = lp.use_wg, split = pp.split, hybrid = pp.hybrid;
     const size_t W = e->w, H = e->h, plane = W * H;
     const int C = e->channels, P = n_frames * C;
@@ -559,6 +578,22 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
 #undef ICER_LAUNCH_LIST
         HIP_TRY(hipEventRecord(e->join[part], e->side_stream));
     }
+    // a quality-targeted call: the families' residual energies, from the coefficients the coder kernels are about to read.  On the side
+    // stream, behind the list kernel if there is one: beside the coder kernels, not in front of them.  (No side stream: before the scan.)
+    const uint32_t tgt_planes = (uint32_t)n_planes;
+    unsigned long long *const dist = target ? e->dist.p + (size_t)f0 * e->plan.n_families * (tgt_planes + 1u) : nullptr;
+    auto launch_energy = [&](hipStream_t es) -> int {
+        HIP_TRY(hipMemsetAsync(dist, 0, (size_t)n_frames * e->plan.n_families * (tgt_planes + 1u) * sizeof(unsigned long long), es));
+        hipLaunchKernelGGL(family_energy_kernel, dim3((unsigned)(e->plan.sig_blocks.size() / 2), n_frames), dim3(64 * kEnergyWaves), 0, es,
+                           reinterpret_cast<const uint16_t *>(coef), plane, (uint32_t)W, C, e->units.p, e->sig_blocks.p, dist, e->plan.n_families, tgt_planes);
+        return 0;
+    };
+    if (target && e->side_stream) {
+        HIP_TRY(hipEventRecord(e->energy_fork[part], st));
+        HIP_TRY(hipStreamWaitEvent(e->side_stream, e->energy_fork[part], 0));
+        if (launch_energy(e->side_stream)) return ICER_FATAL_ERROR;
+        HIP_TRY(hipEventRecord(e->energy_join[part], e->side_stream));
+    }
     SplitLaunch sp;
     if (split) {
         sp.subs = e->subs.p; sp.launch = e->sub_order.p; sp.n_subs = pp.subs; sp.entries = (uint32_t)sub_entries;
@@ -600,7 +635,16 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
     if (timed && e->timing) HIP_TRY(hipEventRecord(e->ev[3], st));
 
     // ---- quota scan + gather into final stream order
-    if (!ladder || ladder->n == 1) {
+    if (target) {
+        if (e->side_stream) HIP_TRY(hipStreamWaitEvent(st, e->energy_join[part], 0));
+        else if (launch_energy(st)) return ICER_FATAL_ERROR;
+        const size_t off_pitch = (size_t)e->max_frames * n_units;
+        hipLaunchKernelGGL(scan_target_kernel, dim3(n_frames, target->n), dim3(64), 0, st, unit_bits, e->final_order.p, n_units, target->thresholds,
+                           (uint64_t)quota, skip, final_off, off_pitch, d_sizes, d_rcs, (uint32_t)target->pitch, e->units.p, bound_ovf, dist,
+                           e->fam_weight.p, e->plan.n_families, tgt_planes, e->fam_ll_term.p, e->fam_chan.p, means, C, target->d_reached + f0, target->d_dist + f0, target->d_equiv + f0);
+        hipLaunchKernelGGL(gather_ladder_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
+                           e->units.p, n_units, unit_bits, final_off, off_pitch, (uint32_t)target->n, d_out, out_stride, (uint32_t)target->pitch);
+    } else if (!ladder || ladder->n == 1) {
         hipLaunchKernelGGL(scan_kernel, dim3(n_frames), dim3(64), 0, st, unit_bits, e->final_order.p, n_units,
                            (uint64_t)quota, skip, final_off, d_sizes, d_rcs, e->units.p, bound_ovf);
         hipLaunchKernelGGL(gather_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
@@ -765,6 +809,9 @@ void icerx_encoder_destroy(icerx_encoder *e)
     e->final_off.release(); e->slots.release(); e->tables.release(); e->in.release(); e->in8.release(); e->out.release();
     e->sizes.release(); e->rcs.release(); e->prof.release();
     e->subs.release(); e->sub_order.release(); e->snap_valid.release(); e->snaps.release(); e->sub_recs.release();
+    e->dist.release(); e->fam_weight.release(); e->fam_chan.release(); e->fam_ll_term.release();
+    for (auto &ev : e->energy_fork) if (ev) (void)hipEventDestroy(ev);
+    for (auto &ev : e->energy_join) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
     if (e->done) (void)hipEventDestroy(e->done);
     for (auto &ev : e->fork) if (ev) (void)hipEventDestroy(ev);
@@ -1034,6 +1081,109 @@ int icerx_encode_device_ladder(icerx_encoder *e, const void *d_frames, int n_fra
     }
     EncodeCall c{planes, n_frames, top, d_out, out_stride, d_sizes, d_rcs, st, true, &lq};
     return encode_sync(e, c, caller_rows);
+}
+
+// Quality-targeted encode (include/icer_hip.h).  T = floor(target_mse x samples x 16) in the units of the frame's distortion D
+// (distortion_core.hpp: Q4 weights), saturated; false: the target is negative or not a number.
+static bool target_threshold(const icerx_encoder *e, double target_mse, uint64_t *T)
+{
+    if (!(target_mse >= 0.0)) return false;
+    const double t = target_mse * (double)((uint64_t)e->w * e->h * (uint64_t)e->channels * 16u);     // (the sample count x 16 < 2^40: exact)
+    *T = t >= 18446744073709551616.0 ? ~0ull : (uint64_t)t;
+    return true;
+}
+
+uint64_t icerx_target_threshold(const icerx_encoder *e, double target_mse)
+{
+    uint64_t T = 0;
+    return e && target_threshold(e, target_mse, &T) ? T : 0;
+}
+
+// What the first target call of an encoder makes: the families' weights on the device, the energy table, the events of the energy
+// pass -- after checking that the frame's distortion cannot leave 64 bits: D <= sum over families of coefficients x (2^15 - 1)^2 x weight (128^2 for the uint8 twins).
+static int prepare_target(icerx_encoder *e)
+{
+    const size_t n_fam = e->plan.n_families, entries = (size_t)(e->sample_bits == 8 ? kPlanes8 : kPlanes) + 1;
+    if (e->fam_weight.p) return 0;
+    std::vector<uint32_t> weight(n_fam, 0u), chan(n_fam, 0u);
+    std::vector<unsigned long long> ll_term(n_fam, 0ull);
+    const uint64_t max_mag = e->sample_bits == 8 ? 128u : 32767u;        // (int8 / int16 coefficients in sign-magnitude form)
+    unsigned __int128 bound = 0;
+    for (const UnitDesc &u : e->plan.units) {
+        if (weight[u.family]) continue;
+        weight[u.family] = kSubbandGainQ4[e->filt][u.level - 1][u.subband];
+        chan[u.family] = u.chan;
+        bound += (unsigned __int128)((uint64_t)u.w * u.h) * (max_mag * max_mag) * weight[u.family];
+        if (u.subband == kLL && e->sample_bits == 16) {      // (the LL mean's upper byte, lost in the packet header: at most 0x7F00 per coefficient)
+            ll_term[u.family] = (unsigned long long)u.w * u.h * weight[u.family];
+            bound += (unsigned __int128)ll_term[u.family] * (0x7F00ull * 0x7F00ull);
+        }
+    }
+    if (bound >> 64) {
+        set_error("icerx_encode_device_target: the distortion of a %zu x %zu frame of %d channel(s) can exceed 64 bits", e->w, e->h, e->channels);
+        return ICER_INVALID_INPUT;
+    }
+    for (int k = 0; k < kMaxParts; k++) {
+        if (!e->energy_fork[k]) HIP_TRY(hipEventCreateWithFlags(&e->energy_fork[k], hipEventDisableTiming));
+        if (!e->energy_join[k]) HIP_TRY(hipEventCreateWithFlags(&e->energy_join[k], hipEventDisableTiming));
+    }
+    if (e->dist.ensure((size_t)e->max_frames * n_fam * entries)) return ICER_FATAL_ERROR;
+    if (e->fam_chan.ensure(n_fam) || e->fam_ll_term.ensure(n_fam)) return ICER_FATAL_ERROR;
+    if (hipMemcpy(e->fam_chan.p, chan.data(), n_fam * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(e->fam_ll_term.p, ll_term.data(), n_fam * sizeof(unsigned long long), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("icerx_encode_device_target: uploading the family tables failed");
+        return ICER_FATAL_ERROR;
+    }
+    DevBuf<uint32_t> w;
+    if (w.ensure(n_fam)) return ICER_FATAL_ERROR;
+    if (hipMemcpy(w.p, weight.data(), n_fam * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) { w.release(); set_error("icerx_encode_device_target: uploading the weights failed"); return ICER_FATAL_ERROR; }
+    e->fam_weight = w;           // (last: its presence says that everything above exists)
+    return 0;
+}
+
+int icerx_encode_device_target(icerx_encoder *e, const void *d_frames, int n_frames, const double *target_mse, int n_targets, size_t byte_cap,
+                               uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, int32_t *d_reached, uint64_t *d_dist,
+                               uint64_t *d_equiv_quota, void *stream)
+{
+    if (int rc = enter_encode("icerx_encode_device_target", e, d_frames && target_mse && d_out && d_sizes && d_rcs && d_reached && d_dist && d_equiv_quota &&
+                              n_targets >= 1 && n_targets <= ICERX_MAX_LADDER, n_frames, 0, 0, " (1 <= n_targets <= ICERX_MAX_LADDER, 1 <= n_frames <= max_frames)")) return rc;
+    Target tg;
+    tg.n = n_targets;
+    tg.pitch = n_frames;
+    tg.d_reached = d_reached;
+    tg.d_dist = reinterpret_cast<unsigned long long *>(d_dist);
+    tg.d_equiv = reinterpret_cast<unsigned long long *>(d_equiv_quota);
+    for (int t = 0; t < n_targets; t++)
+        if (!target_threshold(e, target_mse[t], &tg.thresholds.t[t])) {
+            set_error("icerx_encode_device_target: target %d is negative or not a number", t);
+            return ICER_INVALID_INPUT;
+        }
+    if (int rc = prepare_target(e)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_units(e, byte_cap, st)) return ICER_FATAL_ERROR;
+    if (!stride_admissible(e, out_stride, byte_cap)) {
+        set_error("icerx_encode_device_target: out_stride %zu smaller than the byte cap %zu", out_stride, byte_cap);
+        return ICER_INVALID_INPUT;
+    }
+    if (n_targets > 1 && e->final_off.ensure((size_t)n_targets * e->max_frames * e->plan.units.size())) return ICER_FATAL_ERROR;
+    const uint16_t *planes = static_cast<const uint16_t *>(d_frames);
+    if (e->sample_bits == 8) {          // (as icerx_encode_device_s8)
+        if (convert_samples(e, Convert::S8, static_cast<const uint8_t *>(d_frames), (size_t)n_frames * e->channels * e->w * e->h, st)) return ICER_FATAL_ERROR;
+        planes = e->in.p;
+    }
+    e->dist_frames = n_frames;
+    EncodeCall c{planes, n_frames, byte_cap, d_out, out_stride, d_sizes, d_rcs, st, true, nullptr, &tg};
+    return encode_sync(e, c, caller_rows);
+}
+
+int icerx_get_distortion_table(icerx_encoder *e, int frame, uint64_t *dst, size_t n_entries)
+{
+    if (!e || !dst || !e->dist.p || frame < 0 || frame >= e->dist_frames) return ICER_INVALID_INPUT;
+    const size_t per_frame = (size_t)e->plan.n_families * ((size_t)(e->sample_bits == 8 ? kPlanes8 : kPlanes) + 1);
+    if (n_entries != per_frame) return ICER_INVALID_INPUT;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(dst, e->dist.p + (size_t)frame * per_frame, per_frame * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // The 8-bit front ends: converted into the encoder's own planes on `stream`, then icerx_encode_device on those.

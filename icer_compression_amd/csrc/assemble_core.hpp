@@ -255,12 +255,13 @@ ICER_DEV uint32_t quota_cut_wave(const uint32_t *bits, uint32_t n_units, uint64_
     return K;
 }
 
-ICER_DEV int scan_frame_wave(const uint32_t *bits, const uint32_t *final_order, uint32_t n_units, uint64_t quota,
-                             uint64_t *final_off, uint32_t *kept, uint64_t *size_used)
+// The second half of the walk: final stream offsets of the units [0, K) that a cut keeps (final_off[u] = ~0 for the others) and the
+// stream length; the reference return code of that cut.  Shared by every rule that picks K (the byte quota here, a distortion
+// target in distortion_core.hpp).
+ICER_DEV int final_offsets_wave(const uint32_t *bits, const uint32_t *final_order, uint32_t n_units, uint32_t K,
+                                uint64_t *final_off, uint64_t *size_used)
 {
     DECL_LANE;
-    const uint32_t K = quota_cut_wave(bits, n_units, quota);
-    // final stream offsets
     uint64_t off = 0;
     for (uint32_t base = 0; base < n_units; base += 64) {
         LANEVAR(uint64_t, sz); LANEVAR(uint64_t, before); LANEVAR(uint32_t, unit);
@@ -279,9 +280,16 @@ ICER_DEV int scan_frame_wave(const uint32_t *bits, const uint32_t *final_order, 
         }
         off += total;
     }
-    *kept = K;
     *size_used = off;
     return K < n_units ? kByteQuotaExceeded : kOk;
+}
+
+ICER_DEV int scan_frame_wave(const uint32_t *bits, const uint32_t *final_order, uint32_t n_units, uint64_t quota,
+                             uint64_t *final_off, uint32_t *kept, uint64_t *size_used)
+{
+    const uint32_t K = quota_cut_wave(bits, n_units, quota);
+    *kept = K;
+    return final_offsets_wave(bits, final_order, n_units, K, final_off, size_used);
 }
 
 }  // namespace icer

@@ -6,6 +6,7 @@
 // quota, with progressive mode (if any) stopped at it -- hold every unit that any smaller quota keeps, and each
 // quota's stream is scan + gather over the same slots ("Rate ladder").
 //
+//   drop_frame_wave    a skipped frame, a frame with a failed unit: no stream
 //   scan_ladder_wave   scan_kernel's per-frame work at one quota (frame skip, failed units, quota walk, slot-bound
 //                      check), one wavefront
 //   copy_unit_ladder   gather_kernel's per-unit copy to every quota's stream that keeps the unit, the source words read once
@@ -23,6 +24,32 @@ struct LadderQuotas {
     uint64_t q[kMaxLadder];
 };
 
+// A frame that has no stream -- it was skipped (integer overflow) or one of its units reported an internal error (which makes the
+// frame fail loudly): every final offset ~0, *size 0, *rc the reason.  Returns false for any other frame, nothing written;
+// *flags |= 2 for a failed unit.
+ICER_DEV bool drop_frame_wave(const uint32_t *bits, uint32_t n_units, int skip, uint64_t *foff, unsigned long long *size, int32_t *rc,
+                              uint32_t *flags)
+{
+    DECL_LANE;
+    bool drop = skip != 0;
+    if (!drop) {
+        LANEVAR(int, failed);
+        FOR_LANES
+        {
+            LV(failed) = 0;
+            for (uint32_t i = (uint32_t)lane; i < n_units; i += 64) LV(failed) |= bits[i] == kUnitFailed;
+        }
+        if (BALLOT(LV(failed))) { drop = true; *flags |= 2; }
+    }
+    if (!drop) return false;
+    FOR_LANES
+    {
+        for (uint32_t i = (uint32_t)lane; i < n_units; i += 64) foff[i] = ~0ull;
+        if (lane == 0) { *size = 0; *rc = skip ? kIntegerOverflow : kFatalError; }
+    }
+    return true;
+}
+
 // One frame at one quota: final offsets `foff`, stream length *size and return code *rc, as scan_kernel writes them.
 // Returns the bits to OR into the slot-bound flag: 1 the cut lands on a unit that outgrew a slot sized by the
 // bits-per-pixel bound (the batch is redone with larger slots), 2 a unit reported an internal error.
@@ -31,24 +58,7 @@ ICER_DEV uint32_t scan_ladder_wave(const uint32_t *bits, const uint32_t *final_o
 {
     DECL_LANE;
     uint32_t flags = 0;
-    bool drop = skip != 0;
-    if (!drop) {     // any unit that reported an internal error makes the frame fail loudly
-        LANEVAR(int, failed);
-        FOR_LANES
-        {
-            LV(failed) = 0;
-            for (uint32_t i = (uint32_t)lane; i < n_units; i += 64) LV(failed) |= bits[i] == kUnitFailed;
-        }
-        if (BALLOT(LV(failed))) { drop = true; flags = 2; }
-    }
-    if (drop) {
-        FOR_LANES
-        {
-            for (uint32_t i = (uint32_t)lane; i < n_units; i += 64) foff[i] = ~0ull;
-            if (lane == 0) { *size = 0; *rc = skip ? kIntegerOverflow : kFatalError; }
-        }
-        return flags;
-    }
+    if (drop_frame_wave(bits, n_units, skip, foff, size, rc, &flags)) return flags;
     uint32_t kept;
     uint64_t used;
     const int r = scan_frame_wave(bits, final_order, n_units, quota, foff, &kept, &used);

@@ -6,6 +6,7 @@
 //   code_units_kernel                   context modeller + entropy coder + framing (a-9..a-15)
 //   scan_kernel / gather_kernel         quota cut + final stream order (a-16, a-17)
 //   scan_ladder_kernel / gather_ladder_kernel   the same at several quotas over one coded batch (assemble_ladder.hpp)
+//   family_energy_kernel / scan_target_kernel   the cut where a distortion target is met (distortion_core.hpp)
 // HBM layout: planes are row-major int16/uint16 with row stride = image width; plane p of a batch
 // is frame-major then channel (p = frame * channels + chan).
 #pragma once
@@ -14,6 +15,7 @@
 #include "assemble_core.hpp"
 #include "assemble_ladder.hpp"
 #include "coder_core.hpp"
+#include "distortion_core.hpp"
 #include "coder_wg.hpp"
 #include "coder_wg_small.hpp"
 #include "dwt_tile.hpp"
@@ -826,6 +828,44 @@ gather_ladder_kernel(const uint8_t *__restrict__ slots, size_t slot_frame_stride
     const uint32_t len = kHeaderBytes + ((unit_bits[(size_t)frame * n_units + ui] + 7u) >> 3);
     copy_unit_ladder(slots + (size_t)frame * slot_frame_stride + units[ui].slot_off, len, offs, off_pitch, n_q,
                      out + (size_t)frame * out_stride, (size_t)pitch * out_stride, threadIdx.x, 256u);
+}
+
+// ------------------------------------------------------------------------------------------ distortion target
+// The streams of one coded batch cut where distortion targets are met (icerx_encode_device_target), target-major as the
+// ladder is quota-major.
+
+// E[frame][family][0 .. P] (zeroed before the launch): one workgroup per entry of Plan::sig_blocks -- 4096 coefficients of one
+// family -- and frame.  grid = (blocks, frames), block = 64 * kEnergyWaves.
+__global__ void __launch_bounds__(64 * kEnergyWaves)
+family_energy_kernel(const uint16_t *__restrict__ coef, size_t plane, uint32_t img_w, int channels, const UnitDesc *__restrict__ units,
+                     const uint32_t *__restrict__ sig_blocks, unsigned long long *__restrict__ E, uint32_t n_families, uint32_t P)
+{
+    __shared__ EnergyShared s;
+    const uint32_t frame = blockIdx.y;
+    const UnitDesc &u = units[sig_blocks[2u * blockIdx.x]];
+    const uint32_t blk = sig_blocks[2u * blockIdx.x + 1u];
+    energy_block_wave(s, coef + ((size_t)frame * channels + u.chan) * plane, img_w, u, blk, threadIdx.x >> 6, (uint32_t)kEnergyWaves, P);
+    __syncthreads();
+    energy_block_commit(s, (uint32_t)kEnergyWaves, P, E + ((size_t)frame * n_families + u.family) * (P + 1u), threadIdx.x);
+}
+
+// One wavefront per (frame, target): grid = (frames, targets), block = 64.  `reached`, `dist`, `equiv`: rows as sizes / rcs.
+__global__ void __launch_bounds__(64)
+scan_target_kernel(const uint32_t *__restrict__ unit_bits, const uint32_t *__restrict__ final_order, uint32_t n_units, TargetList targets,
+                   uint64_t byte_cap, const int *__restrict__ frame_skip, uint64_t *__restrict__ final_off, size_t off_pitch,
+                   unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs, uint32_t pitch, const UnitDesc *__restrict__ units,
+                   int *__restrict__ bound_overflow, const unsigned long long *__restrict__ E, const uint32_t *__restrict__ fam_weight,
+                   uint32_t n_families, uint32_t P, const unsigned long long *__restrict__ fam_ll_term, const uint32_t *__restrict__ fam_chan,
+                   const uint16_t *__restrict__ means, int channels, int32_t *__restrict__ reached, unsigned long long *__restrict__ dist,
+                   unsigned long long *__restrict__ equiv)
+{
+    const uint32_t frame = blockIdx.x, t = blockIdx.y;
+    const size_t row = (size_t)t * pitch + frame;
+    const uint32_t flags = scan_target_wave(unit_bits + (size_t)frame * n_units, final_order, n_units, targets.t[t], byte_cap, frame_skip[frame],
+                                            units, E + (size_t)frame * n_families * (P + 1u), fam_weight, n_families, P,
+                                            fam_ll_term, fam_chan, means + (size_t)frame * channels, final_off + (size_t)t * off_pitch + (size_t)frame * n_units, sizes + row, rcs + row,
+                                            reached + row, dist + row, equiv + row);
+    if (flags && threadIdx.x == 0) atomicOr(bound_overflow, (int)flags);
 }
 
 }  // namespace icer

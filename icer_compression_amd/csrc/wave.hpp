@@ -44,6 +44,10 @@ static inline uint32_t brev32(uint32_t v) { uint32_t r = 0; for (int i = 0; i < 
 #define WAVE_XOR(DST, X) { DST = 0; for (int l_ = 0; l_ < 64; ++l_) DST ^= X[l_]; }
 #define WAVE_MAX(DST, X) { DST = 0; for (int l_ = 0; l_ < 64; ++l_) DST = X[l_] > DST ? X[l_] : DST; }
 #define WAVE_EXCL_SCAN(T, OUT, IN, TOTAL) { T run_ = 0; for (int l_ = 0; l_ < 64; ++l_) { const T v_ = IN[l_]; OUT[l_] = run_; run_ += v_; } TOTAL = run_; }
+// DST = the sum of a 64-bit lane variable over the wave (the same value in every lane)
+#define WAVE_SUM64(DST, X) { DST = 0; for (int l_ = 0; l_ < 64; ++l_) DST += X[l_]; }
+// *PTR += VAL on a 64-bit word of global memory that other workgroups add to as well
+#define GLOBAL_ADD64(PTR, VAL) (*(PTR) += (VAL))
 #else
 // ------------------------------------------------------------------ gfx950 (product)
 #include <hip/hip_runtime.h>
@@ -76,4 +80,6 @@ static __device__ __forceinline__ uint32_t brev32(uint32_t v) { return __brev(v)
 #define WAVE_EXCL_SCAN(T, OUT, IN, TOTAL) { const T v_ = (IN); T s_ = v_; \
     for (int o_ = 1; o_ < 64; o_ <<= 1) { const T u_ = (T)__shfl_up(s_, o_); if (lane >= o_) s_ += u_; } \
     OUT = s_ - v_; TOTAL = (T)__shfl(s_, 63); }
+#define WAVE_SUM64(DST, X) { unsigned long long t_ = (X); for (int o_ = 32; o_ > 0; o_ >>= 1) t_ += (unsigned long long)__shfl_xor((long long)t_, o_); DST = t_; }
+#define GLOBAL_ADD64(PTR, VAL) ((void)atomicAdd(reinterpret_cast<unsigned long long *>(PTR), (unsigned long long)(VAL)))
 #endif

@@ -153,6 +153,46 @@ int icerx_encode_device(icerx_encoder *enc, const uint16_t *d_frames, int n_fram
 int icerx_encode_device_ladder(icerx_encoder *enc, const void *d_frames, int n_frames, const size_t *quotas, int n_quotas,
                                uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream);
 
+/* Quality-targeted encode: every frame is cut where a distortion target is met, or at byte_cap if that comes first -- ICER's
+ * two stopping rules.  The batch is transformed and coded once, planned as a call at byte_cap; one extra pass over the
+ * coefficient planes gives every family -- a (channel, level, subband, segment) rectangle -- the squared error E[family][b]
+ * that is left when its bit planes >= b are kept (b = 0 .. P, P = 9 coded planes, 7 for sample_bits = 8; the decoder rebuilds
+ * magnitudes by truncation, so these are exact integers), and the frame's distortion after a prefix of its packets is
+ *     D = sum over families of weight(filter, level, subband) * E[family][lowest plane kept, or P]  +  M
+ * with the Q4 subband weights of csrc/subband_gain.hpp (the three channels of a YUV frame count equally).  M is what no packet
+ * takes out: the packet header has ONE byte for a channel's LL mean (lib_icer's format), so a decoder gets every LL coefficient
+ * of a 16-bit frame back short by (mean & 0xFF00); M = sum over LL families of weight * coefficients * (mean & 0xFF00)^2, and
+ * 0 for frames whose LL means are below 256 and for sample_bits = 8.  D / 16 estimates the squared error of the decoded image.
+ * Accuracy, measured against the reference decoder wherever the actual error is at least 1 per sample
+ * (profiles/quality_target.md): within 6.0 dB in the worst case -- a lone large coefficient near the frame's edge, whose
+ * weight differs from the subband's --, within about 1 dB where the error is made of many coefficients.  The inverse
+ * transform's integer rounding is not modelled.
+ * A stream keeps the shortest prefix of the packets in priority order with D <= T, T = icerx_target_threshold(target).
+ *   d_frames      as icerx_encode_device_ladder takes them; not modified
+ *   target_mse    HOST array of n_targets mean squared errors per sample, 1 <= n_targets <= ICERX_MAX_LADDER, in any order,
+ *                 repeats allowed; T = floor(target_mse * w * h * channels * 16), saturated to 64 bits
+ *   byte_cap      the byte quota no stream exceeds (plays the role of the ladder's largest quota; out_stride likewise)
+ *   d_out, d_sizes, d_rcs   target-major exactly as the ladder's are quota-major: frame f at target t is row / entry
+ *                 t * n_frames + f.  rc: ICER_BYTE_QUOTA_EXCEEDED when packets were left out, ICER_RESULT_OK otherwise
+ *   d_reached     device pointer, n_targets * n_frames int32: 1 the target was met, 0 the byte cap ended the stream first
+ *   d_dist        device pointer, n_targets * n_frames uint64: D of the stream
+ *   d_equiv_quota device pointer, n_targets * n_frames uint64: a byte quota at which icerx_encode_device (or _s8, the
+ *                 reference encoder, icerx_recut_device_async on a longer stream) produces this very stream
+ * A frame without a stream (ICER_INTEGER_OVERFLOW) has d_reached 0, d_dist 0 and d_equiv_quota = byte_cap.  Synchronous, with
+ * the same re-runs as the ladder.  Returns 0, ICER_INVALID_INPUT (nothing enqueued or written: n_targets or n_frames out of
+ * range, a null pointer, a negative or NaN target, an asynchronous encode pending, out_stride too small, or a geometry
+ * whose D could exceed 64 bits -- DESIGN.md 3 "Distortion target") or ICER_FATAL_ERROR (HIP failure).
+ * The table E lives in encoder-owned device memory made by the first such call; an encoder that never makes one pays nothing.
+ *
+ * icerx_target_threshold: the integer T a target becomes for this encoder (0 for a negative or NaN target).
+ * icerx_get_distortion_table: host copy of frame `frame`'s E of the last target call, n_entries = families * (P + 1) uint64,
+ * entry family * (P + 1) + b, families in the order their first packet has in the priority order (M is not part of the table). */
+int icerx_encode_device_target(icerx_encoder *enc, const void *d_frames, int n_frames, const double *target_mse, int n_targets,
+                               size_t byte_cap, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs,
+                               int32_t *d_reached, uint64_t *d_dist, uint64_t *d_equiv_quota, void *stream);
+uint64_t icerx_target_threshold(const icerx_encoder *enc, double target_mse);
+int icerx_get_distortion_table(icerx_encoder *enc, int frame, uint64_t *dst, size_t n_entries);
+
 /* The same call in two halves.  icerx_encode_device_async returns as soon as all work is enqueued on `stream`;
  * icerx_encoder_wait returns once it has completed there (re-running the batch in the rare cases the synchronous call
  * does: a coding unit that outgrew its slot, a unit time-out).  Between the two the caller may enqueue its own copies
