@@ -308,10 +308,14 @@ class Encoder:
         """the integer threshold a target becomes (icerx_target_threshold): floor(target_mse * samples * 16)"""
         return int(self.lib.icerx_target_threshold(self.handle, float(target_mse)))
 
-    def distortion_table(self, frame: int = 0) -> np.ndarray:
-        """the families' residual energies of `frame` in the last target call (icerx_get_distortion_table): uint64 (families, P + 1)"""
+    def distortion_table(self, frame: int = 0, families: int | None = None) -> np.ndarray:
+        """the families' residual energies of `frame` in the last target call (icerx_get_distortion_table): uint64 (families, P + 1).
+        families: the rows of the table; by default units / P, which holds unless a subband has fewer samples than there are
+        segments -- its planes then keep the rectangles of whichever packet comes before them in the priority order, every
+        distinct rectangle is a family (csrc/plan.hpp, quirk P1), and the caller has to give the count."""
         planes = 7 if self.sample_bits == 8 else 9
-        families = self.info()["units_per_frame"] // planes          # (a family = the coded planes of one rectangle, csrc/plan.hpp)
+        if families is None:
+            families = self.info()["units_per_frame"] // planes      # (a family = the coded planes of one rectangle, csrc/plan.hpp)
         dst = np.zeros((families, planes + 1), np.uint64)
         rc = self.lib.icerx_get_distortion_table(self.handle, frame, dst.ctypes.data, dst.size)
         if rc != 0:

@@ -15,6 +15,7 @@ TOO_BIG, FAILED = 0xFFFFFFFF, 0xFFFFFFFE
 NONE = 0xFFFFFFFFFFFFFFFF
 LL, HL, LH, HH = range(4)
 QUOTA_EXCEEDED = -5
+MAX_SEGMENTS = 32
 
 
 def coded_planes(bits: int) -> int:
@@ -36,9 +37,22 @@ def dim_high(d, level):
     return dim_low(d, level - 1) // 2
 
 
-def grid_rects(w, h, s):
-    """the segments of a w x h subband in coding order (make_grid + grid_rects of csrc/plan.hpp)"""
-    assert 1 <= s <= w * h
+def grid_fails(w, h, s) -> bool:
+    """make_grid of csrc/plan.hpp refuses: more segments than the subband has samples, or than the format allows"""
+    return s > w * h or s > MAX_SEGMENTS
+
+
+def subband_rect(w, h, level, sb):
+    """(width, height, x offset, y offset) of a subband in plane coordinates"""
+    lw, lh = dim_low(w, level), dim_low(h, level)
+    sw, ox = (lw, 0) if sb in (LL, LH) else (dim_high(w, level), lw)
+    sh, oy = (lh, 0) if sb in (LL, HL) else (dim_high(h, level), lh)
+    return sw, sh, ox, oy
+
+
+def grid_rows(w, h, s):
+    """(rows, columns of a top row, top rows) of the grid of a w x h subband; rows below the top ones have a column more"""
+    assert s >= 1 and not grid_fails(w, h, s)
     if h > (s - 1) * w:
         r = s
     else:
@@ -46,7 +60,12 @@ def grid_rects(w, h, s):
         while r < s and (r + 1) * r * w < h * s:
             r += 1
     c = s // r
-    r_t = (c + 1) * r - s
+    return r, c, (c + 1) * r - s
+
+
+def grid_rects(w, h, s):
+    """the segments of a w x h subband in coding order (make_grid + grid_rects of csrc/plan.hpp)"""
+    r, c, r_t = grid_rows(w, h, s)
     h_t = max(((2 * h * c * r_t + s) // 2) // s, r_t)
     x_t = w // c
     c_t0 = (x_t + 1) * c - w
@@ -103,19 +122,33 @@ def packets(stages, channels, planes):
     return sorted(pk, key=lambda p: (-p[4], p[1]))
 
 
+class Refused(ValueError):
+    """the planner refuses the geometry: the grid of the very first packet fails (the reference reads an uninitialised one)"""
+
+
 class Model:
     """units[k] = (chan, level, subband, lsb, seg, family, priority) in priority order; families[f] = (chan, x0, y0, w, h, weight);
-    ll_term[f] = weight x coefficients of an LL family of a 16-bit geometry, else 0 (the LL mean's loss, below)"""
+    ll_term[f] = weight x coefficients of an LL family of a 16-bit geometry, else 0 (the LL mean's loss, below).
+
+    Quirk P1 (build_plan of csrc/plan.hpp): the packets are walked in priority order, and a packet whose subband has fewer
+    samples than there are segments keeps the rectangles of the packet before it, laid at its own subband's origin.  Which
+    packet came before depends on the bit plane, so the planes of one (channel, level, subband, segment) can have different
+    rectangles: a family is keyed by the rectangle as well.  stale = the packets (level, subband, lsb, chan) that kept a grid."""
 
     def __init__(self, w, h, channels, stages, filt, segments, bits=16):
         self.w, self.h, self.channels, self.bits, self.P = w, h, channels, bits, coded_planes(bits)
         gains = committed_weights()
         self.units, self.families, self.ll_term, index = [], [], [], {}
+        self.stale, rects = [], None
         for (lv, sb, lsb, ch, prio) in packets(stages, channels, self.P):
-            lw, lh = dim_low(w, lv), dim_low(h, lv)
-            sw, ox = (lw, 0) if sb in (LL, LH) else (dim_high(w, lv), lw)
-            sh, oy = (lh, 0) if sb in (LL, HL) else (dim_high(h, lv), lh)
-            for sg, (x, y, rw, rh) in enumerate(grid_rects(sw, sh, segments)):
+            sw, sh, ox, oy = subband_rect(w, h, lv, sb)
+            if not grid_fails(sw, sh, segments):
+                rects = grid_rects(sw, sh, segments)
+            elif rects is None:
+                raise Refused((w, h, channels, stages, segments, bits))
+            else:
+                self.stale.append((lv, sb, lsb, ch))
+            for sg, (x, y, rw, rh) in enumerate(rects):
                 key = (ch, lv, sb, sg, ox + x, oy + y, rw, rh)
                 if key not in index:
                     index[key] = len(self.families)

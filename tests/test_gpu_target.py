@@ -57,7 +57,7 @@ def check_call(orc, enc, g, model, specs, t, targets, cap, got, what):
     """checks 1-3 of a finished call; returns the (target, frame) pairs whose target was met below the cap"""
     n = t.shape[0]
     at_cap = separate(enc, t, cap)
-    tables = [enc.distortion_table(f) for f in range(n)]        # (before any other target call; separate calls leave it alone)
+    tables = [enc.distortion_table(f, model.n_families) for f in range(n)]   # (before any other target call; separate calls leave it alone)
     memo = {cap: at_cap}
     met = []
     for f in range(n):
@@ -160,6 +160,29 @@ def test_target_streams_tables_and_cuts(oracle, monkeypatch, name, cap_class):
         assert rc == 0 and frames[0][:3] == frames[1][:3] == (0, g.w, g.h)
         assert all(np.array_equal(a, b) for a, b in zip(frames[0][3], frames[1][3]))
         dec.close()
+    assert enc.stats()["unit_timeouts"] == 0
+    enc.close()
+
+
+@pytest.mark.timeout(300)
+def test_kept_grid_geometry_has_more_families_than_segments(oracle):
+    """71 x 172 YUV, 5 stages, 16 segments (found by tests/test_gpu_geometry_sweep.py): the level-5 subbands have fewer samples
+    than segments, their planes keep the rectangles of the packet before them (quirk P1, csrc/plan.hpp) and every distinct
+    rectangle is a family: the energy table has more rows than units / 9"""
+    g = ebc.Geometry(71, 172, 3, 5, 6, 16)
+    specs = [("wide", 0), ("noise8", 1), ("smooth", 0)]
+    model = tm.Model(g.w, g.h, g.channels, g.stages, g.filt, g.segments)
+    assert model.stale and model.n_families > model.n_units // 9
+    enc = api.Encoder(g.w, g.h, g.channels, g.stages, g.filt, g.segments, max_frames=3)
+    assert enc.info()["units_per_frame"] == model.n_units
+    t = device_frames(ebc.batch(g, specs))
+    targets, cap = [0.0, 40.0, HUGE], ebc.quota(g, "lossless")
+    got = target(enc, t, targets, cap)
+    with pytest.raises(api.IcerHipError):
+        enc.distortion_table(1)                                  # (units / 9 rows: not this geometry's table)
+    assert enc.distortion_table(1, model.n_families).shape == (model.n_families, 10)
+    met, _, _ = check_call(oracle, enc, g, model, specs, t, targets, cap, got, "kept grid")
+    assert len(met) >= 3
     assert enc.stats()["unit_timeouts"] == 0
     enc.close()
 
