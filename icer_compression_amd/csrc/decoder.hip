@@ -257,6 +257,8 @@ finish_kernel(uint16_t *__restrict__ planes, size_t frame_stride, int channels, 
 
 }  // namespace
 
+#include "decoder_display.hpp"         // display_finish_kernel: the last pass of the *_display calls, in finish_kernel's place
+
 // ------------------------------------------------------------------------------------------ decoder object
 // The side streams carry the kernels of the ring size classes side by side with the plane kernel on the call's own stream.  The HIP runtime
 // shares GPU_MAX_HW_QUEUES (4 by default) hardware queues PER PRIORITY LEVEL out over the live streams of the process, and streams on one
@@ -287,7 +289,7 @@ struct icerx_decoder {
     uint32_t crc_tab[256];
     // device buffers, grown on demand and kept
     struct Buf { void *p = nullptr; size_t cap = 0; };
-    Buf data, frames, crc, dtables, count, cands, chains, work, tmp, out8, pos, list, err;
+    Buf data, frames, crc, dtables, count, cands, chains, work, tmp, out8, pos, list, err, disp;
     int n_cus = 256;                   // compute units of the device
     bool planes_lds_raised = false;    // decode_chains_planes_kernel has been granted more than 64 KiB of dynamic LDS
     int is_gfx950 = -1;                // (-1: not asked yet)
@@ -370,11 +372,14 @@ size_t resolve_planes_lds(icerx_decoder *d)
 // data_on_device).  Results: rcs[k], ws[k] / hs[k] (in: the values kept when stream k holds no valid packet).  Frame k's
 // channel c goes to host_out[k * channels + c] (host pointers, >= frame_stride samples each) or, when host_out is null, to
 // dev_out + (k * channels + c) * frame_stride samples (device memory; uint16 or uint8 samples by sample_bits).
+// Display calls (host_out and dev_out null): frame k's 8-bit image (decoder_display.hpp) goes to disp_host[k] (host pointers,
+// channels * frame_stride bytes each) or, when disp_host is null, to disp_dev + k * channels * frame_stride bytes.
 int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_device, const size_t *offsets, const size_t *lens,
-                 void *const *host_out, void *dev_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
+                 void *const *host_out, void *dev_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs,
+                 uint8_t *const *disp_host = nullptr, uint8_t *disp_dev = nullptr)
 {
     g_error.clear();
-    if (!d || n < 0 || (n && (!offsets || !lens || !rcs || !ws || !hs)) || (!host_out && !dev_out && n)) return ICER_INVALID_INPUT;
+    if (!d || n < 0 || (n && (!offsets || !lens || !rcs || !ws || !hs)) || (!host_out && !dev_out && !disp_host && !disp_dev && n)) return ICER_INVALID_INPUT;
     if (n == 0) return ICER_RESULT_OK;
     int rc = ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits, stages = d->stages;
@@ -641,6 +646,19 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
         }
 
         // 5. results
+        if (disp_host || disp_dev) {                         // a display call: finished and converted in one pass
+            uint8_t *d_img = disp_dev;
+            if (disp_host) { HIP_TRY(ensure(d->disp, planes_total)); d_img = (uint8_t *)d->disp.p; }
+            ICER_LAUNCH(display_finish_kernel, dim3((unsigned)(((frame_stride + 3u) / 4u + 255u) / 256u), (unsigned)n), 256, 0, d_planes,
+                        frame_stride, channels, d_frames, bits, d_img);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipDeviceSynchronize());
+            for (int k = 0; k < n && disp_host; k++) {
+                const size_t bytes = (size_t)channels * frames[k].w * frames[k].h;
+                if (bytes) HIP_TRY(hipMemcpy(disp_host[k], d_img + (size_t)k * channels * frame_stride, bytes, hipMemcpyDeviceToHost));
+            }
+            goto done;
+        }
         if (bits == 8) {
             if (dev_out && !host_out) d_out8 = (uint8_t *)dev_out;
             else { HIP_TRY(ensure(d->out8, planes_total)); d_out8 = (uint8_t *)d->out8.p; }
@@ -733,7 +751,7 @@ void icerx_decoder_destroy(icerx_decoder *d)
 {
     if (!d) return;
     for (icerx_decoder::Buf *b : {&d->data, &d->frames, &d->crc, &d->dtables, &d->count, &d->cands, &d->chains, &d->work, &d->tmp,
-                                  &d->out8, &d->pos, &d->list, &d->err})
+                                  &d->out8, &d->pos, &d->list, &d->err, &d->disp})
         if (b->p) (void)hipFree(b->p);
 #ifndef ICER_HOST_MOCK
     if (d->side_ok) for (hipStream_t st : d->side) (void)hipStreamDestroy(st);
@@ -761,7 +779,77 @@ int icerx_decode_device(icerx_decoder *dec, int n, const void *d_data, const siz
     return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, nullptr, d_out, frame_stride, rcs, ws, hs);
 }
 
+int icerx_decode_host_display(icerx_decoder *dec, int n, const uint8_t *data, const size_t *offsets, const size_t *lens,
+                              uint8_t *const *images_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
+{
+    if (!images_out && n) return ICER_INVALID_INPUT;
+    for (int k = 0; k < n; k++)
+        if (!images_out[k]) return ICER_INVALID_INPUT;
+    return decode_batch(dec, n, data, false, offsets, lens, nullptr, nullptr, frame_stride, rcs, ws, hs, images_out, nullptr);
+}
+
+int icerx_decode_device_display(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
+                                uint8_t *d_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
+{
+    if (!d_out && n) return ICER_INVALID_INPUT;
+    return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, nullptr, nullptr, frame_stride, rcs, ws, hs, nullptr, d_out);
+}
+
+int icerx_planes_to_display_device(const void *d_planes, int n_frames, int channels, size_t w, size_t h, size_t plane_stride,
+                                   int sample_bits, uint8_t *d_out, size_t frame_stride, void *stream)
+{
+    g_error.clear();
+    if (!d_planes || !d_out || n_frames < 0 || (channels != 1 && channels != 3) || (sample_bits != 16 && sample_bits != 8)) return ICER_INVALID_INPUT;
+    if (w && h > (size_t)-1 / w) return ICER_INVALID_INPUT;
+    const size_t pixels = w * h;
+    if (pixels > plane_stride || pixels > frame_stride) return ICER_INVALID_INPUT;       // (a frame stays inside its planes and its row)
+    if (n_frames == 0 || pixels == 0) return ICER_RESULT_OK;
+    const int sample_bytes = sample_bits / 8;
+    const size_t group = 8u / (size_t)sample_bytes, blocks = ((pixels + group - 1u) / group + 255u) / 256u;
+    if (blocks > 0x7FFFFFFFull) return fail("frames of %zu pixels: too many for one launch", pixels);
+    for (int first = 0; first < n_frames; first += (int)kDisplayFramesPerLaunch) {
+        const unsigned count = (unsigned)std::min<int>(n_frames - first, (int)kDisplayFramesPerLaunch);
+        ICER_LAUNCH_ON((hipStream_t)stream, display_planes_kernel, dim3((unsigned)blocks, count), 256, 0,
+                       (const void *)((const uint8_t *)d_planes + (size_t)first * channels * plane_stride * sample_bytes), plane_stride,
+                       channels, sample_bytes, pixels, d_out + (size_t)first * channels * frame_stride, frame_stride);
+        if (hipGetLastError() != hipSuccess) return fail("display_planes_kernel could not be launched");
+    }
+    return ICER_RESULT_OK;
+}
+
+int icerx_decompress_display(uint8_t *image, size_t *image_w, size_t *image_h, size_t image_bufsize_pixels,
+                             const uint8_t *datastream, size_t data_length, uint8_t stages, enum icer_filter_types filt,
+                             uint8_t segments, int channels)
+{
+    if (!image || !image_w || !image_h || (!datastream && data_length) || (channels != 1 && channels != 3)) return ICER_INVALID_INPUT;
+    icerx_decoder *d = nullptr;
+    int rc = icerx_decoder_create(&d, -1, channels, stages, (int)filt, segments, 16);
+    if (rc != ICER_RESULT_OK) return rc;
+    const size_t off = 0;
+    int frame_rc = ICER_RESULT_OK;
+    uint8_t *const images[1] = {image};
+    rc = decode_batch(d, 1, datastream, false, &off, &data_length, nullptr, nullptr, image_bufsize_pixels, &frame_rc, image_w, image_h, images, nullptr);
+    icerx_decoder_destroy(d);
+    return rc != ICER_RESULT_OK ? rc : frame_rc;
+}
+
 #ifdef ICER_DECODE_ASYNC
+size_t icerx_decode_display_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t frame_stride)
+{
+    if (!dec || n <= 0) return 0;
+    return async_layout(dec, n, data_bytes, frame_stride, true).total;
+}
+
+int icerx_decode_device_display_async(icerx_decoder *dec, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                      size_t stream_stride, const uint64_t *d_lens, uint8_t *d_out, size_t frame_stride,
+                                      int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs, void *d_workspace, size_t workspace_bytes,
+                                      void *stream)
+{
+    if (!d_out && n > 0) return ICER_INVALID_INPUT;
+    return decode_async(dec, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, nullptr, frame_stride, d_rcs,
+                        d_ws, d_hs, d_workspace, workspace_bytes, (hipStream_t)stream, d_out);
+}
+
 size_t icerx_decode_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t frame_stride)
 {
     if (!dec || n <= 0) return 0;

@@ -47,7 +47,9 @@ DPlanGeom async_geom(const icerx_decoder *d)
     return DPlanGeom{(uint32_t)d->channels, (uint32_t)d->stages, d->segments, (uint32_t)(d->bits == 8 ? kPlanes8 : kPlanes)};
 }
 
-AsyncLayout async_layout(const icerx_decoder *d, int n, size_t data_bytes, size_t frame_stride)
+// `display`: a display call (icerx_decode_device_display_async) -- its working planes live in the workspace whatever the sample
+// width, as an 8-bit decoder's do
+AsyncLayout async_layout(const icerx_decoder *d, int n, size_t data_bytes, size_t frame_stride, bool display = false)
 {
     AsyncLayout L;
     const DPlanGeom g = async_geom(d);
@@ -72,7 +74,7 @@ AsyncLayout async_layout(const icerx_decoder *d, int n, size_t data_bytes, size_
     L.chains = take(sizeof(ChainDesc) * N * L.chain_slots);
     L.lists = take(sizeof(uint32_t) * N * L.chain_slots);
     L.tmp = take(sizeof(uint16_t) * planes_total);
-    L.work = take(d->bits == 8 ? sizeof(uint16_t) * planes_total : 0u);
+    L.work = take(d->bits == 8 || display ? sizeof(uint16_t) * planes_total : 0u);
     L.pos = take(sizeof(uint32_t) * N * L.pos_words);
     L.total = at;
     return L;
@@ -422,15 +424,16 @@ constexpr uint32_t kGridCus = 2;                  // (the mock's persistent grid
 
 int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
                  const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs,
-                 void *workspace, size_t workspace_bytes, hipStream_t st)
+                 void *workspace, size_t workspace_bytes, hipStream_t st, uint8_t *d_display = nullptr)
 {
+    // (d_display: a display call -- d_out is null, the images go to d_display through display_finish_kernel)
     g_error.clear();
     if (!d || n < 0) return ICER_INVALID_INPUT;
     if (n == 0) return ICER_RESULT_OK;
-    if (!d_lens || !d_out || !d_rcs || !d_ws || !d_hs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
+    if (!d_lens || (!d_out && !d_display) || !d_rcs || !d_ws || !d_hs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
     if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
     if (frame_stride > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", frame_stride);
-    const AsyncLayout L = async_layout(d, n, data_bytes, frame_stride);
+    const AsyncLayout L = async_layout(d, n, data_bytes, frame_stride, d_display != nullptr);
     if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
     int rc = ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits, stages = d->stages;
@@ -448,7 +451,7 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     const DecoderTables *tables = (const DecoderTables *)d->dtables.p;
     const uint32_t blob_len = (uint32_t)data_bytes, slots = (uint32_t)n * L.chain_slots;
     const size_t planes_total = (size_t)n * channels * frame_stride;
-    uint16_t *planes = bits == 16 ? (uint16_t *)d_out : (uint16_t *)(ws + L.work);
+    uint16_t *planes = bits == 16 && !d_display ? (uint16_t *)d_out : (uint16_t *)(ws + L.work);
 #ifdef ICER_HOST_MOCK
     const uint32_t cus = kGridCus;
 #else
@@ -596,7 +599,11 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
                 HIP_TRY(hipGetLastError());
             }
         }
-        ICER_LAUNCH_ON(st, finish_kernel, grid_all, 256, 0, planes, frame_stride, channels, frames, bits == 8 ? (uint8_t *)d_out : nullptr);
+        if (d_display)
+            ICER_LAUNCH_ON(st, display_finish_kernel, dim3((unsigned)(((frame_stride + 3u) / 4u + 255u) / 256u), (unsigned)n), 256, 0, planes,
+                           frame_stride, channels, frames, bits, d_display);
+        else
+            ICER_LAUNCH_ON(st, finish_kernel, grid_all, 256, 0, planes, frame_stride, channels, frames, bits == 8 ? (uint8_t *)d_out : nullptr);
         HIP_TRY(hipGetLastError());
         ICER_LAUNCH_ON(st, fatal_frames_kernel, ((unsigned)n + 255u) / 256u, 256, 0, ferr, d_rcs, (uint32_t)n);
         HIP_TRY(hipGetLastError());

@@ -38,7 +38,25 @@ def bind(path: str) -> C.CDLL:
                     ("icer_decompress_image_uint8", 1), ("icer_decompress_image_yuv_uint8", 3)):
         getattr(lib, name).argtypes = [C.c_void_p] * n + tail
     lib.icerx_decoder_last_error.restype = C.c_char_p
+    # the display entry points (a build without them still serves everything above)
+    if hasattr(lib, "icerx_decompress_display"):
+        lib.icerx_decompress_display.argtypes = [C.c_void_p] + tail + [C.c_int]
+        lib.icerx_planes_to_display_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _sz, _sz, _sz, C.c_int, C.c_void_p, _sz, C.c_void_p]
+        disp = [C.POINTER(_sz), C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(C.c_int), C.POINTER(_sz), C.POINTER(_sz)]
+        lib.icerx_decode_host_display.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + disp
+        lib.icerx_decode_device_display.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + disp
+    if hasattr(lib, "icerx_decode_device_display_async"):
+        lib.icerx_decode_display_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, _sz]
+        lib.icerx_decode_display_workspace_bytes.restype = _sz
+        lib.icerx_decode_device_display_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, _sz,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
     return lib
+
+
+def _need(lib, name):
+    if not hasattr(lib, name):
+        raise RuntimeError(f"this build of the decoder library has no {name}")
+    return getattr(lib, name)
 
 
 def load_library() -> C.CDLL:
@@ -77,6 +95,46 @@ def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: i
     return rc, w.value, h.value, planes
 
 
+def decompress_display(stream: bytes, channels: int, stages: int, filt: int, segments: int, lib=None):
+    """icerx_decompress_display on a host 16-bit stream -> (rc, image): uint8 (h, w) for channels 1 (gray8), (h, w, 3) for
+    channels 3 (RGB888), the image the reference's `icer_util decompress` writes; an empty array when nothing was decoded."""
+    lib = lib or load_library()
+    fn = _need(lib, "icerx_decompress_display")
+    rc0, w0, h0 = icer_get_image_dimensions(stream, lib)
+    bufsize = w0 * h0 if rc0 == 0 else 0
+    buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
+    image = np.zeros(max(bufsize * max(channels, 1), 1), np.uint8)
+    w, h = _sz(0), _sz(0)
+    rc = fn(image.ctypes.data, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, channels)
+    if channels not in (1, 3) or w.value * h.value == 0 or w.value * h.value > bufsize:
+        return rc, np.zeros((0, 0) if channels != 3 else (0, 0, 3), np.uint8)
+    image = image[: channels * w.value * h.value]
+    return rc, image.reshape((h.value, w.value) if channels == 1 else (h.value, w.value, 3))
+
+
+def planes_to_display_torch(planes):
+    """icerx_planes_to_display_device on torch's current stream, without waiting: planes = a contiguous cuda tensor
+    (..., channels, h, w) with channels 1 or 3, or (h, w) gray, of int16 / uint16 or uint8 samples taken as unsigned and as
+    they are -> a cuda uint8 tensor (..., h, w) gray8 or (..., h, w, 3) RGB888."""
+    import torch
+    fn = _need(load_library(), "icerx_planes_to_display_device")
+    if planes.dim() == 2:
+        planes = planes[None]
+    want = (torch.int16, getattr(torch, "uint16", torch.int16), torch.uint8)
+    if not planes.is_cuda or not planes.is_contiguous() or planes.dtype not in want or planes.dim() < 3 or planes.shape[-3] not in (1, 3):
+        raise ValueError("planes: a contiguous cuda int16 / uint16 / uint8 tensor (..., 1 or 3, h, w) is needed")
+    ch, h, w = (int(x) for x in planes.shape[-3:])
+    n = planes.numel() // max(ch * h * w, 1) if h * w else 0
+    lead = tuple(planes.shape[:-3])
+    out = torch.empty(lead + ((h, w) if ch == 1 else (h, w, 3)), dtype=torch.uint8, device=planes.device)
+    if n:
+        st = torch.cuda.current_stream(planes.device)
+        rc = fn(planes.data_ptr(), n, ch, w, h, h * w, 8 if planes.dtype == torch.uint8 else 16, out.data_ptr(), h * w, st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_planes_to_display_device: {rc} {load_library().icerx_decoder_last_error().decode()}")
+    return out
+
+
 class Decoder:
     """Batch / device-resident extension (icerx_decoder_*, include/icer_hip_dec.h Part 2)."""
 
@@ -96,6 +154,7 @@ class Decoder:
                                                            C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
                                                            C.c_void_p]
         self._workspaces = {}                # decode_torch: one cached workspace per torch stream
+        self._display_workspaces = {}        # decode_display_torch: the same, sized for the display call
         self.handle = C.c_void_p()
         rc = self.lib.icerx_decoder_create(C.byref(self.handle), device, channels, stages, filt, segments, bits)
         if rc != 0:
@@ -149,6 +208,74 @@ class Decoder:
         lens, ws, hs: uint64 / int64; rcs: int32).  Enqueues on `stream` and returns the call's rc without waiting."""
         return self.lib.icerx_decode_device_async(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_out,
                                                   frame_stride, d_rcs, d_ws, d_hs, d_workspace, workspace_bytes, stream)
+
+    # ---- straight to 8-bit display images: gray8 / packed RGB888 (include/icer_hip_dec.h) ----
+    def decode_display_host(self, streams, frame_stride: int):
+        """icerx_decode_host_display -> (rc, [(rc_k, w_k, h_k, image)]): image = flat uint8 of channels * frame_stride bytes,
+        its first channels * w_k * h_k bytes the gray8 / RGB888 image of frame k"""
+        fn = _need(self.lib, "icerx_decode_host_display")
+        n = len(streams)
+        blob, offs, lens = self._pack(streams)
+        images = [np.zeros(max(self.channels * frame_stride, 1), np.uint8) for _ in range(n)]
+        ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in images])
+        rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
+        rc = fn(self.handle, n, blob.ctypes.data, offs, lens, ptrs, frame_stride, rcs, ws, hs)
+        return rc, [(rcs[k], ws[k], hs[k], images[k]) for k in range(n)]
+
+    def decode_display_device(self, n: int, d_data: int, offsets, lens, d_out: int, frame_stride: int):
+        """icerx_decode_device_display on raw device pointers; frame k's image at d_out + k * channels * frame_stride bytes
+        -> (rc, rcs, ws, hs)"""
+        fn = _need(self.lib, "icerx_decode_device_display")
+        offs = (_sz * max(n, 1))(*[int(o) for o in offsets])
+        ln = (_sz * max(n, 1))(*[int(x) for x in lens])
+        rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
+        rc = fn(self.handle, n, d_data, offs, ln, d_out, frame_stride, rcs, ws, hs)
+        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+
+    def display_workspace_bytes(self, n: int, data_bytes: int, frame_stride: int) -> int:
+        """icerx_decode_display_workspace_bytes: the device workspace one decode_display_async_ptrs call needs"""
+        return int(_need(self.lib, "icerx_decode_display_workspace_bytes")(self.handle, n, data_bytes, frame_stride))
+
+    def decode_display_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, d_out: int,
+                                  frame_stride: int, d_rcs: int, d_ws: int, d_hs: int, d_workspace: int, workspace_bytes: int,
+                                  stream: int = 0) -> int:
+        """icerx_decode_device_display_async on raw device pointers (arguments as decode_device_async_ptrs; d_out: uint8 images)"""
+        return _need(self.lib, "icerx_decode_device_display_async")(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens,
+                                                                    d_out, frame_stride, d_rcs, d_ws, d_hs, d_workspace, workspace_bytes,
+                                                                    stream)
+
+    def decode_display_torch(self, data, lens, out, rcs, ws, hs, offsets=None, stream_stride=None) -> None:
+        """decode_torch with 8-bit images for output (icerx_decode_device_display_async), on torch's current stream, without
+        waiting.  out: a contiguous cuda uint8 tensor of n * frame_stride * channels bytes, e.g. (n, h, w, 3) or (n, h, w);
+        frame k's image is its first channels * ws[k] * hs[k] bytes of row k.  Everything else as decode_torch; the workspace
+        (which holds the working planes) is cached per stream, apart from decode_torch's."""
+        import torch
+        n = int(lens.shape[0])
+        if offsets is None and stream_stride is None:
+            if data.dim() != 2:
+                raise ValueError("a 1-D blob needs offsets or stream_stride")
+            stream_stride = data.stride(0)
+        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("rcs", rcs, torch.int32),
+                            ("ws", ws, torch.int64), ("hs", hs, torch.int64), ("out", out, torch.uint8)) + \
+                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
+                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        if n and out.numel() % (n * self.channels):
+            raise ValueError("out must hold n * frame_stride * channels bytes")
+        frame_stride = out.numel() // (n * self.channels) if n else 0
+        data_bytes = data.numel()
+        st = torch.cuda.current_stream(data.device)
+        need = self.display_workspace_bytes(n, data_bytes, frame_stride) if n else 0
+        work = self._display_workspaces.get(st.cuda_stream)
+        if work is None or work.numel() < max(need, 1):
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
+            self._display_workspaces[st.cuda_stream] = work
+        work.record_stream(st)
+        rc = self.decode_display_async_ptrs(n, data.data_ptr(), data_bytes, offsets.data_ptr() if offsets is not None else None,
+                                            int(stream_stride or 0), lens.data_ptr(), out.data_ptr(), frame_stride, rcs.data_ptr(),
+                                            ws.data_ptr(), hs.data_ptr(), work.data_ptr(), work.numel(), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_decode_device_display_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
 
     def decode_torch(self, data, lens, out, rcs, ws, hs, offsets=None, stream_stride=None) -> None:
         """Decode n streams of a cuda uint8 tensor on torch's current stream, without waiting (icerx_decode_device_async).

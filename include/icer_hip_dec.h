@@ -100,6 +100,59 @@ int icerx_decode_device_async(icerx_decoder *dec, int n, const void *d_data, siz
                               size_t stream_stride, const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs,
                               uint64_t *d_ws, uint64_t *d_hs, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Decoding straight to 8-bit display images ----------------------------------------------------------------------
+ * The counterpart of the encoder's front-end fusion (icerx_encode_device_u8 / _rgb8, icer_hip.h): the decoder's last pass
+ * writes gray8 (1-channel decoders) or packed RGB888 (3-channel decoders) instead of planes, for sample_bits 16 and 8
+ * (csrc/decoder_display.hpp).  With v the sample the plain call delivers, taken as unsigned (uint16, or uint8 for an 8-bit
+ * decoder), and clip clamping to 0..255:
+ *     gray8    min(v, 255), one byte per pixel
+ *     RGB888   R = clip(Y + ((91881 Cr) >> 16) - 179)
+ *              G = clip(Y - ((22544 Cb + 46793 Cr) >> 16) + 135)
+ *              B = clip(Y + ((116129 Cb) >> 16) - 226),       three bytes per pixel in the order R, G, B
+ * -- what the reference's callers compute on the host (example/inc/color_util.h CYCbCr2R/G/B, example/src/icer_util.c
+ * yuv_to_rgb888_packed and :321-326).  The reference evaluates the products in 32-bit int, which overflows (undefined
+ * behaviour) from Cb >= 18 493 or Cr >= 23 373; this library gives the exact integer result for every input 0..65535, which
+ * equals the reference's wherever the reference's is defined.
+ * frame_stride is in PIXELS: frame k's image starts at d_out + k * channels * frame_stride bytes (or is images_out[k]), pixel
+ * i at byte channels * i.  For every frame of every call rcs / ws / hs equal those of the plain call (icerx_decode_device /
+ * _async) on the same input, and the image is the conversion above of the first ws * hs samples the plain call delivers for
+ * the frame -- whatever its return code: damaged and truncated streams and frames that stop before the transform included.
+ * Nothing is written behind channels * ws * hs bytes of a frame's row, in the row of a frame for which the plain call writes
+ * no samples, beyond the n rows, or to the input.  The 32-bit limits of the plain calls apply unchanged. */
+
+/* icerx_decode_host with one host image per frame: images_out[k] holds channels * frame_stride bytes */
+int icerx_decode_host_display(icerx_decoder *dec, int n, const uint8_t *data, const size_t *offsets, const size_t *lens,
+                              uint8_t *const *images_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs);
+
+/* icerx_decode_device with the images in device memory.  Synchronous. */
+int icerx_decode_device_display(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
+                                uint8_t *d_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs);
+
+/* icerx_decode_device_async with the images in d_out, stream-ordered under the same rules (no blocking copy, no
+ * synchronisation, no hipMalloc / hipFree).  The working planes (2 bytes per sample, for either sample width) live in the
+ * caller's workspace: it holds at least icerx_decode_display_workspace_bytes(dec, n, data_bytes, frame_stride) bytes.
+ * ICER_INVALID_INPUT for null arguments or a workspace that is too small: nothing is enqueued or written. */
+size_t icerx_decode_display_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t frame_stride);
+int icerx_decode_device_display_async(icerx_decoder *dec, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                      size_t stream_stride, const uint64_t *d_lens, uint8_t *d_out, size_t frame_stride,
+                                      int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs, void *d_workspace, size_t workspace_bytes,
+                                      void *stream);
+
+/* The conversion alone, for planes already in device memory (callers who processed the planes themselves): frame k's channel
+ * c = w * h samples at d_planes + (k * channels + c) * plane_stride samples (uint16 or uint8 by sample_bits), taken as they
+ * are (no negative-clamping); frame k's image at d_out + k * channels * frame_stride bytes.  Enqueued on `stream`; no
+ * synchronisation.  The same device function as the fused pass.  ICER_INVALID_INPUT -- nothing enqueued -- for null pointers,
+ * channels other than 1 or 3, sample_bits other than 16 or 8, n_frames < 0, or w * h beyond plane_stride or frame_stride. */
+int icerx_planes_to_display_device(const void *d_planes, int n_frames, int channels, size_t w, size_t h, size_t plane_stride,
+                                   int sample_bits, uint8_t *d_out, size_t frame_stride, void *stream);
+
+/* lib_icer-shaped single-stream call for 16-bit streams: `image` (host memory, channels * image_bufsize_pixels bytes)
+ * receives the gray8 (channels 1) or RGB888 (channels 3) image; return codes as icer_decompress_image_[yuv_]uint16, and
+ * ICER_INVALID_INPUT for channels other than 1 or 3. */
+int icerx_decompress_display(uint8_t *image, size_t *image_w, size_t *image_h, size_t image_bufsize_pixels,
+                             const uint8_t *datastream, size_t data_length, uint8_t stages, enum icer_filter_types filt,
+                             uint8_t segments, int channels);
+
 /* ---- Re-cutting stored streams to smaller byte quotas ---------------------------------------------------------------
  * A byte quota decides only where a stream is cut, never what a packet holds.  So from a stored master stream M of a frame
  * -- made by this project's encoders or by the reference at quota Qm, return code ICER_RESULT_OK or

@@ -15,9 +15,9 @@
  * 32-bit, BI_RGB) -- and applies stb_image's channel conversions where the requested mode differs from the file's
  * (gray -> colour: replicate; colour -> gray: (77 r + 150 g + 29 b) >> 8), which is what the reference's CLI gets.
  * `decompress` (the reference: icer_util.c:248-365) needs -c or -G like the reference's, decodes with the stages / filter /
- * segments given (they must be the ones of the stream), clamps gray samples to 255, converts colour back with
- * CYCbCr2R/G/B (example/inc/color_util.h:31-33) and writes -- where the reference writes a BMP through stb_image_write --
- * a 24-bit BMP when the output name ends in .bmp, else a binary PGM / PPM.
+ * segments given (they must be the ones of the stream) straight to the 8-bit image on the GPU (icerx_decompress_display: gray
+ * samples clamped to 255, colour converted back with CYCbCr2R/G/B, example/inc/color_util.h:31-33) and writes -- where the
+ * reference writes a BMP through stb_image_write -- a 24-bit BMP when the output name ends in .bmp, else a binary PGM / PPM.
  *
  * Build:  gcc -O2 -I include tools/icer_util_hip.c -L icer_compression_amd -licer_hip -licer_hip_dec -Wl,-rpath,$PWD/icer_compression_amd
  */
@@ -170,30 +170,19 @@ static int decompress_file(const char *prog, const char *in, const char *out, in
     if (icer_get_image_dimensions(data, (size_t)len, &w, &h) != ICER_RESULT_OK) { fprintf(stderr, "%s: no valid packet in %s\n", prog, in); return 1; }
     printf("image %zu x %zu, decoding as %s with %d stages, filter %d, %d segments\n", w, h, force_color ? "Y Cb Cr" : "gray", stages, (int)filt, segments);
     const size_t n = w * h;
-    uint16_t *pl[3] = {NULL, NULL, NULL};
-    for (int k = 0; k < 3; k++) pl[k] = (uint16_t *)calloc(n, sizeof(uint16_t));
+    /* straight to the 8-bit image on the GPU (icerx_decompress_display: gray clamped at 255, colour through CYCbCr2R/G/B) */
+    uint8_t *px = (uint8_t *)calloc(n * (force_color ? 3 : 1) + 1, 1);
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
-    const int rc = force_color ? icer_decompress_image_yuv_uint16(pl[0], pl[1], pl[2], &aw, &ah, n, data, (size_t)len, (uint8_t)stages, filt, (uint8_t)segments)
-                               : icer_decompress_image_uint16(pl[0], &aw, &ah, n, data, (size_t)len, (uint8_t)stages, filt, (uint8_t)segments);
+    const int rc = icerx_decompress_display(px, &aw, &ah, n, data, (size_t)len, (uint8_t)stages, filt, (uint8_t)segments, force_color ? 3 : 1);
     clock_gettime(CLOCK_MONOTONIC, &t1);
     if (rc != ICER_RESULT_OK) {
         fprintf(stderr, "decode failed: status %d (%s); were -s -f -g the ones the stream was made with?\n", rc, icerx_decoder_last_error());
         return 1;
     }
     printf("decode call took %.3f s\n", (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec));
-    uint8_t *px = (uint8_t *)malloc(n * (force_color ? 3 : 1));
-    for (size_t i = 0; i < aw * ah; i++) {
-        if (force_color) {
-            const int y = pl[0][i], cb = pl[1][i], cr = pl[2][i];
-            px[3 * i] = (uint8_t)clip255(y + ((91881 * cr) >> 16) - 179);
-            px[3 * i + 1] = (uint8_t)clip255(y - ((22544 * cb + 46793 * cr) >> 16) + 135);
-            px[3 * i + 2] = (uint8_t)clip255(y + ((116129 * cb) >> 16) - 226);
-        } else px[i] = pl[0][i] > 255 ? 255 : (uint8_t)pl[0][i];
-    }
     if (save_image(out, px, aw, ah, force_color ? 3 : 1)) { fprintf(stderr, "cannot write %s\n", out); return 1; }
     printf("wrote %s (%zu x %zu, %s)\n", out, aw, ah, force_color ? "colour" : "gray");
-    for (int k = 0; k < 3; k++) free(pl[k]);
     free(px);
     free(data);
     return 0;
