@@ -284,6 +284,9 @@ static hipError_t create_side_stream(hipStream_t *st)
 
 struct icerx_decoder {
     int device = 0, channels = 1, stages = 1, filt = 0, bits = 16;
+    // a reduced-resolution decoder (icerx_decoder_create_reduced): made for streams of stages + reduce stages, it decodes their
+    // derived streams (plan_decode) -- `stages` is what is left to run, and everything below the planners goes by it alone
+    int reduce = 0;
     unsigned segments = 1;
     DecoderTables tables;
     uint32_t crc_tab[256];
@@ -453,7 +456,7 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
             mine.clear();
             while (at < cands.size() && cands[at].frame == (uint32_t)k) mine.push_back(cands[at++]);
             DecodePlan &pl = plans[k];
-            plan_decode(&pl, mine, channels, stages, d->segments, bits, ws[k], hs[k], frame_stride);
+            plan_decode(&pl, mine, channels, stages, d->segments, bits, ws[k], hs[k], frame_stride, d->reduce);
             ws[k] = pl.w; hs[k] = pl.h; rcs[k] = pl.rc;
             const bool runs = !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
             frames[k].w = runs ? (uint32_t)pl.w : 0u;
@@ -685,13 +688,13 @@ done:
 }
 
 int decompress_planes(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
-                      const uint8_t *data, size_t data_length, int stages, int filt, unsigned segments, int bits)
+                      const uint8_t *data, size_t data_length, int stages, int filt, unsigned segments, int bits, int reduce = 0)
 {
     if (!image_w || !image_h || (!data && data_length)) return ICER_INVALID_INPUT;
     for (int c = 0; c < channels; c++)
         if (!planes[c]) return ICER_INVALID_INPUT;
     icerx_decoder *d = nullptr;
-    int rc = icerx_decoder_create(&d, -1, channels, stages, filt, segments, bits);
+    int rc = icerx_decoder_create_reduced(&d, -1, channels, stages, filt, segments, bits, reduce);
     if (rc != ICER_RESULT_OK) return rc;
     const size_t off = 0;
     int frame_rc = ICER_RESULT_OK;
@@ -713,11 +716,27 @@ const char *icerx_decoder_last_error(void) { return g_error.c_str(); }
 
 int icerx_decoder_create(icerx_decoder **out, int device, int channels, int stages, int filt, unsigned segments, int sample_bits)
 {
+    return icerx_decoder_create_reduced(out, device, channels, stages, filt, segments, sample_bits, 0);
+}
+
+int icerx_decoder_reduce(const icerx_decoder *dec) { return dec ? dec->reduce : 0; }
+
+void icerx_reduced_size(size_t w, size_t h, int reduce, size_t *rw, size_t *rh)
+{
+    const int r = reduce < 0 ? 0 : reduce > 63 ? 63 : reduce;
+    if (rw) *rw = (w >> r) + ((w & (((size_t)1 << r) - 1u)) ? 1u : 0u);          // (ceil(w / 2^r) without the overflow of w + 2^r - 1)
+    if (rh) *rh = (h >> r) + ((h & (((size_t)1 << r) - 1u)) ? 1u : 0u);
+}
+
+int icerx_decoder_create_reduced(icerx_decoder **out, int device, int channels, int stages, int filt, unsigned segments, int sample_bits,
+                                 int reduce)
+{
     g_error.clear();
     if (!out) return ICER_INVALID_INPUT;
     *out = nullptr;
     if ((channels != 1 && channels != 3) || filt < 0 || filt > 6 || (sample_bits != 8 && sample_bits != 16)) return ICER_INVALID_INPUT;
     if (stages < 1 || stages > kMaxStages) return ICER_TOO_MANY_STAGES;        // (reference: out-of-bounds table)
+    if (reduce < 0 || reduce >= stages) return ICER_INVALID_INPUT;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no usable HIP device");
 #ifndef ICER_HOST_MOCK
@@ -727,7 +746,7 @@ int icerx_decoder_create(icerx_decoder **out, int device, int channels, int stag
     }
 #endif
     icerx_decoder *d = new icerx_decoder;
-    d->device = device; d->channels = channels; d->stages = stages; d->filt = filt; d->bits = sample_bits; d->segments = segments;
+    d->device = device; d->channels = channels; d->stages = stages - reduce; d->reduce = reduce; d->filt = filt; d->bits = sample_bits; d->segments = segments;
 #ifndef ICER_HOST_MOCK
     { int cur = 0; hipDeviceProp_t prop; if (hipGetDevice(&cur) == hipSuccess && hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) d->n_cus = prop.multiProcessorCount; }
 #endif
@@ -881,6 +900,15 @@ int icer_get_image_dimensions(const uint8_t *datastream, size_t data_length, siz
         return ICER_RESULT_OK;
     }
     return ICER_DECODER_OUT_OF_DATA;
+}
+
+int icerx_decompress_reduced(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
+                             const uint8_t *datastream, size_t data_length, uint8_t stages, enum icer_filter_types filt,
+                             uint8_t segments, int sample_bits, int reduce)
+{
+    if (!planes || (channels != 1 && channels != 3)) return ICER_INVALID_INPUT;
+    return decompress_planes(planes, channels, image_w, image_h, bufsize, datastream, data_length, stages, (int)filt, segments,
+                             sample_bits, reduce);
 }
 
 int icer_decompress_image_uint16(uint16_t *image, size_t *image_w, size_t *image_h, size_t image_bufsize,

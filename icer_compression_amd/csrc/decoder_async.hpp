@@ -44,7 +44,8 @@ struct AsyncLayout {
 
 DPlanGeom async_geom(const icerx_decoder *d)
 {
-    return DPlanGeom{(uint32_t)d->channels, (uint32_t)d->stages, d->segments, (uint32_t)(d->bits == 8 ? kPlanes8 : kPlanes)};
+    return DPlanGeom{(uint32_t)d->channels, (uint32_t)d->stages, d->segments, (uint32_t)(d->bits == 8 ? kPlanes8 : kPlanes),
+                     (uint32_t)d->reduce};
 }
 
 // `display`: a display call (icerx_decode_device_display_async) -- its working planes live in the workspace whatever the sample

@@ -20,9 +20,11 @@ namespace icer {
 struct DCandRec { uint32_t off, crc; };           // blob offset of a header candidate, CRC-32 of its payload (0: does not fit)
 
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+constexpr uint32_t kDroppedSlot = 0xFFFFFFFEu;    // DCand::slot of a valid packet that a reduced-resolution decoder steps over
 constexpr uint32_t kNoChain = 0xFFFFFFFFu;        // ChainDesc::frame of an empty chain slot
 
-// the packet table and chain slots of one frame, for one decoder configuration
+// the packet table and chain slots of one frame, for one decoder configuration.  reduce = r > 0 (a reduced-resolution
+// decoder): stages is the decoder's S - r and the walk reads a frame as its derived stream, as plan_decode does.
 struct DPlanGeom {
     uint32_t channels, stages, segments, planes;
     ICER_HD uint32_t slots() const { return channels * (stages + 1u) * 4u * segments * (uint32_t)kPlanes; }
@@ -32,6 +34,7 @@ struct DPlanGeom {
     }
     // chain slot j = ((lv - 1) * channels + ch) * 4 * segments + sb * segments + sg: plan_decode's order
     ICER_HD uint32_t chain_slots() const { return stages * channels * 4u * segments; }
+    uint32_t reduce;
 };
 
 // ---- segment grid: make_grid / grid_rects of plan.hpp, callable on the device, one rectangle at a time
@@ -103,6 +106,7 @@ ICER_HD bool dheader_at(const uint32_t *crc_tab, const uint8_t *blob, uint32_t b
 }
 // what the walk of frame [frame_off, frame_off + frame_len) needs of one candidate: where it starts and ends in the frame,
 // its table slot and fields.  end = 0: not a packet of this frame (header or payload outside it, payload CRC wrong).
+// slot = kDroppedSlot: a packet of the frame at a level the decoder leaves out; it moves the cursor and sets nothing.
 struct DCand {
     uint32_t rel, end, slot, bits, w, h, mean_ch;   // mean_ch: mean | channel << 16 (channel 3 and up: none)
 };
@@ -115,10 +119,11 @@ ICER_HD DCand dplan_summary(const DPlanGeom &g, const uint8_t *blob, uint32_t fr
     const uint32_t bits = load_le32(p + 16), pb = bits / 8u + ((bits % 8u) ? 1u : 0u);
     if (pb > frame_len - d.rel - (uint32_t)kHeaderBytes || r.crc != load_le32(p + 20)) return d;   // (icer_compress.c:576-577)
     d.end = d.rel + (uint32_t)kHeaderBytes + pb;
-    const uint32_t lv = p[4], sb = p[5], sg = p[6], lsb = p[7] & 15u, ch = g.channels == 3 ? (uint32_t)(p[7] >> 4) : 0u;
+    if ((uint32_t)p[4] <= g.reduce && g.reduce > 0u) { d.slot = kDroppedSlot; return d; }
+    const uint32_t lv = p[4] - g.reduce, sb = p[5], sg = p[6], lsb = p[7] & 15u, ch = g.channels == 3 ? (uint32_t)(p[7] >> 4) : 0u;
     if (lv <= g.stages && sb < 4u && sg < g.segments && lsb < (uint32_t)kPlanes && ch < g.channels) d.slot = g.slot(ch, lv, sb, sg, lsb);
     d.bits = bits;
-    d.w = load_le32(p + 8); d.h = load_le32(p + 12);
+    d.w = (uint32_t)reduced_dim(load_le32(p + 8), (int)g.reduce); d.h = (uint32_t)reduced_dim(load_le32(p + 12), (int)g.reduce);
     d.mean_ch = (uint32_t)(p[2] | (p[3] << 8)) | ((ch < 3u ? ch : 3u) << 16);
     return d;
 }
@@ -138,10 +143,11 @@ ICER_HD void dwalk_init(DWalk *s, uint64_t w_in, uint64_t h_in)
 ICER_HD void dplan_accept(DWalk *s, const DCand &c, uint32_t *tab_off, uint32_t *tab_bits)
 {
     if (c.end == 0 || c.rel < s->cursor) return;
+    s->cursor = c.end;
+    if (c.slot == kDroppedSlot) return;
     if (c.slot != kNoSlot) { tab_off[c.slot] = c.rel; tab_bits[c.slot] = c.bits; }
     s->w = c.w; s->h = c.h;
     if ((c.mean_ch >> 16) < 3u) s->mean[c.mean_ch >> 16] = (uint16_t)(c.mean_ch & 0xFFFFu);
-    s->cursor = c.end;
 }
 
 // first candidate at or behind blob offset `off` (recs sorted by offset)

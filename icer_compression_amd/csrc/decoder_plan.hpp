@@ -105,6 +105,9 @@ ICER_HD uint32_t payload_piece_crc(const uint32_t *tab, const uint8_t *s, const 
     return v;
 }
 
+// a side of the image at 1 / 2^r size: ceil(v / 2^r) (r < kMaxStages)
+ICER_HD uint64_t reduced_dim(uint64_t v, int r) { return (v + ((uint64_t(1) << r) - 1)) >> r; }
+
 struct DecodeLevel { uint32_t cw, ch; };        // region of one inverse-transform level (deepest first)
 
 struct DecodePlan {
@@ -117,8 +120,11 @@ struct DecodePlan {
 };
 
 // `cands`: the candidates of ONE stream, sorted by offset.  *w / *h: in = the caller's values (kept when the stream holds no valid packet).
+// `reduce` = r > 0 (a reduced-resolution decoder, include/icer_hip_dec.h): `stages` is the decoder's S - r, and the walk reads
+// the stream as its derived stream -- a valid packet of level <= r moves the cursor and nothing else, any other counts as
+// level - r of an image of ceil(w / 2^r) x ceil(h / 2^r).
 inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cands, int channels,
-                        int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize)
+                        int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce = 0)
 {
     const int planes = sample_bits == 8 ? kPlanes8 : kPlanes;
     *pl = DecodePlan();
@@ -138,15 +144,16 @@ inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cand
     for (const PacketCandidate &c : cands) {
         if (c.off < cursor || !c.fits || !c.payload_ok) continue;
         const uint8_t *p = c.hdr;
-        const int lv = p[4], sb = p[5], sg = p[6], lsb = p[7] & 15, ch = channels == 3 ? (p[7] >> 4) : 0;
+        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
+        if ((int)p[4] <= reduce && reduce > 0) continue;          // (dropped from the derived stream)
+        const int lv = p[4] - reduce, sb = p[5], sg = p[6], lsb = p[7] & 15, ch = channels == 3 ? (p[7] >> 4) : 0;
         if (lv <= kMaxStages && sb < 4 && sg <= kMaxSegments && lsb < kPlanes && ch < 3) {
             slot(ch, lv, sb, sg, lsb) = c.off;
             bits_tab[slot_index(ch, lv, sb, sg, lsb)] = load_le32(p + 16);
         }
-        pl->w = load_le32(p + 8);
-        pl->h = load_le32(p + 12);
+        pl->w = reduced_dim(load_le32(p + 8), reduce);
+        pl->h = reduced_dim(load_le32(p + 12), reduce);
         if (ch < 3) pl->mean[ch] = (uint16_t)(p[2] | (p[3] << 8));
-        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
     }
     if (bufsize < pl->w * pl->h) { pl->rc = kByteQuotaExceeded; return; }
     const size_t w = pl->w, h = pl->h;

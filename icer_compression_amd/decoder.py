@@ -50,6 +50,13 @@ def bind(path: str) -> C.CDLL:
         lib.icerx_decode_display_workspace_bytes.restype = _sz
         lib.icerx_decode_device_display_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, _sz,
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
+    # decoding at 1/2^r resolution
+    if hasattr(lib, "icerx_decoder_create_reduced"):
+        lib.icerx_decoder_create_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
+        lib.icerx_decoder_reduce.argtypes = [C.c_void_p]
+        lib.icerx_reduced_size.argtypes = [_sz, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz)]
+        lib.icerx_reduced_size.restype = None
+        lib.icerx_decompress_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int] + tail + [C.c_int, C.c_int]
     return lib
 
 
@@ -78,17 +85,31 @@ def icer_get_image_dimensions(stream: bytes, lib=None):
     return rc, w.value, h.value
 
 
+def reduced_size(w: int, h: int, r: int):
+    """the size of a w x h image decoded at 1/2^r resolution: (ceil(w / 2^r), ceil(h / 2^r)) (icerx_reduced_size)"""
+    return (w + (1 << r) - 1) >> r, (h + (1 << r) - 1) >> r
+
+
 def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: int, bufsize: int | None = None, bits: int = 16,
-               lib=None):
-    """icer_decompress_image_[yuv_]uint16 / _uint8 on a host stream -> (rc, w, h, [flat planes of bufsize samples])."""
+               lib=None, reduce: int = 0):
+    """icer_decompress_image_[yuv_]uint16 / _uint8 on a host stream -> (rc, w, h, [flat planes of bufsize samples]).
+    reduce = r > 0: icerx_decompress_reduced, the image at 1/2^r size; bufsize then counts samples of the reduced image."""
     lib = lib or load_library()
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
     if bufsize is None:
         rc, w, h = icer_get_image_dimensions(stream, lib)
+        if reduce > 0:
+            w, h = reduced_size(w, h, reduce)
         bufsize = w * h if rc == 0 else 0
     buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
     planes = [np.zeros(max(bufsize, 1), np.uint16 if bits == 16 else np.uint8) for _ in range(channels)]
+    if reduce != 0:
+        fn = _need(lib, "icerx_decompress_reduced")
+        ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
+        w, h = _sz(0), _sz(0)
+        rc = fn(ptrs, channels, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, bits, reduce)
+        return rc, w.value, h.value, planes
     fn = getattr(lib, "icer_decompress_image_" + ("yuv_" if channels == 3 else "") + ("uint16" if bits == 16 else "uint8"))
     w, h = _sz(0), _sz(0)
     rc = fn(*[p.ctypes.data for p in planes], C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments)
@@ -138,9 +159,12 @@ def planes_to_display_torch(planes):
 class Decoder:
     """Batch / device-resident extension (icerx_decoder_*, include/icer_hip_dec.h Part 2)."""
 
-    def __init__(self, channels: int, stages: int, filt: int, segments: int, bits: int = 16, device: int = -1, lib=None):
+    def __init__(self, channels: int, stages: int, filt: int, segments: int, bits: int = 16, device: int = -1, lib=None,
+                 reduce: int = 0):
+        """reduce = r > 0: a decoder for streams made with `stages` that delivers every image at 1/2^r size
+        (icerx_decoder_create_reduced): strides and buffer sizes count samples of the reduced image, ws / hs report its size"""
         self.lib = lib or load_library()
-        self.channels, self.bits = channels, bits
+        self.channels, self.bits, self.reduce = channels, bits, 0
         self.lib.icerx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int]
         self.lib.icerx_decoder_destroy.argtypes = [C.c_void_p]
         self.lib.icerx_decoder_destroy.restype = None
@@ -156,6 +180,15 @@ class Decoder:
         self._workspaces = {}                # decode_torch: one cached workspace per torch stream
         self._display_workspaces = {}        # decode_display_torch: the same, sized for the display call
         self.handle = C.c_void_p()
+        if reduce != 0:
+            fn = _need(self.lib, "icerx_decoder_create_reduced")
+            fn.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
+            self.lib.icerx_decoder_reduce.argtypes = [C.c_void_p]
+            rc = fn(C.byref(self.handle), device, channels, stages, filt, segments, bits, reduce)
+            if rc != 0:
+                raise RuntimeError(f"icerx_decoder_create_reduced: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+            self.reduce = int(self.lib.icerx_decoder_reduce(self.handle))
+            return
         rc = self.lib.icerx_decoder_create(C.byref(self.handle), device, channels, stages, filt, segments, bits)
         if rc != 0:
             raise RuntimeError(f"icerx_decoder_create: {rc} {self.lib.icerx_decoder_last_error().decode()}")

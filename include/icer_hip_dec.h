@@ -4,7 +4,8 @@
  * STATUS: bit-exact against the decoder oracle in its CPU builds (tests/test_emu_decoder.py) and on an MI355X
  * (tests/test_gpu_decoder.py: gray / YUV, 16 / 8 bit, damaged and truncated streams, wrong decode parameters, the golden
  * decoder digests up to 4096 x 4096, the batch object, all three decode kernels; the reference-held fixtures and the
- * reference's own example programs linked against this library, tests/test_gpu_parity.py / test_gpu_examples.py).
+ * reference's own example programs linked against this library, tests/test_gpu_parity.py / test_gpu_examples.py; decoding at
+ * 1/2^r resolution, tests/test_reduced_mock.py / test_gpu_reduced.py).
  * Speed (round 4, bench.py `decode` object and tools/decode_bench.py; HISTORY.md 6b (summary: DESIGN.md 8)): a chain (segment of a subband) is a serial
  * adaptive decode, one decision at a time per bit plane.  One 4096 x 4096 headline stream: 55 Mpix/s (303 ms; one wavefront per
  * bit plane with wave-uniform decisions, decoder_planes.hpp) = 14 x the reference decoder on one core of the same box; the
@@ -152,6 +153,36 @@ int icerx_planes_to_display_device(const void *d_planes, int n_frames, int chann
 int icerx_decompress_display(uint8_t *image, size_t *image_w, size_t *image_h, size_t image_bufsize_pixels,
                              const uint8_t *datastream, size_t data_length, uint8_t stages, enum icer_filter_types filt,
                              uint8_t segments, int channels);
+
+/* ---- Decoding at 1/2^r resolution --------------------------------------------------------------------------------------
+ * A stream made with S stages holds the image at 1/2 .. 1/2^(S-1) size as the low-pass corner of its coefficient pyramid.  A
+ * reduced decoder (0 <= r < S) never starts the entropy chains of levels 1 .. r -- level 1 alone is 3/4 of all samples -- and
+ * runs S - r inverse stages on what is left.  What it delivers is DEFINED through the derived stream X_r of a stream X:
+ *     walk X with the decoder's cursor rule (a CRC-valid packet is stepped over whole, anything else byte by byte; every valid
+ *     packet takes part in the walk); keep, in order, the valid packets of decomp_level > r; in each kept header set
+ *     decomp_level -= r, image_w = ceil(image_w / 2^r), image_h = ceil(image_h / 2^r) and recompute the header CRC; payloads
+ *     and payload CRCs stay.
+ * The reduced decode of X at r is the plain decode of X_r by a decoder made for (S - r stages, the same filter, segments and
+ * sample width): image, size, return code, damaged and truncated streams, a frame whose valid packets are all dropped (it
+ * keeps the size in-values, like an empty stream) included.  That is exact, not an approximation: ceil(ceil(w / 2^r) / 2^k) =
+ * ceil(w / 2^(r + k)), so the level-k subbands of the reduced image have the sizes -- and therefore the segment grids -- of
+ * the level-(r + k) subbands of the full one; the context model goes by subband type alone; the LL mean travels in the
+ * header.  The image is the top-left LL_r corner the full decode holds after S - r of its S inverse stages, with negative
+ * samples clamped to zero at that size.  (A chain whose packets do not decode within their own payloads -- coefficients
+ * above the coded bit planes -- reads on into the bytes that follow in X, as the plain decode does.) */
+
+/* A decoder for streams made with `stages`, delivering every image at 1/2^reduce size.  0 <= reduce < stages, else
+ * ICER_INVALID_INPUT; reduce 0 is icerx_decoder_create.  Every entry point that takes the decoder then works on the reduced
+ * image: host, device, async, the three display calls, and the two workspace-size functions.  frame_stride / bufsize are
+ * measured against ceil(w / 2^r) * ceil(h / 2^r), and ws / hs / d_ws / d_hs report the reduced size. */
+int icerx_decoder_create_reduced(icerx_decoder **out, int device, int channels, int stages, int filt, unsigned segments,
+                                 int sample_bits, int reduce);
+int icerx_decoder_reduce(const icerx_decoder *dec);                                /* the decoder's reduce (0 for NULL) */
+void icerx_reduced_size(size_t w, size_t h, int reduce, size_t *rw, size_t *rh);   /* host helper, ceil(w / 2^r) */
+/* lib_icer-shaped one-shot: planes[c] host memory of bufsize samples (uint16 / uint8 by sample_bits), channels 1 or 3 */
+int icerx_decompress_reduced(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
+                             const uint8_t *datastream, size_t data_length, uint8_t stages, enum icer_filter_types filt,
+                             uint8_t segments, int sample_bits, int reduce);
 
 /* ---- Re-cutting stored streams to smaller byte quotas ---------------------------------------------------------------
  * A byte quota decides only where a stream is cut, never what a packet holds.  So from a stored master stream M of a frame
