@@ -9,6 +9,12 @@
 //   packets    recut_gather_kernel, one workgroup per (unit, frame): the packet copied verbatim to every quota's stream
 //              that keeps it (copy_unit_recut)
 // Everything is enqueued on the caller's stream; the caller owns the workspace (recut_layout).
+//
+// icerx_recut_device_cuts_async cuts by resolution as well: a cut is (reduce r, quota), the re-cut of the master's derived
+// stream at 1/2^r size.  Its frames step (recut_cuts_plan_kernel) makes the packet table once and runs every cut's walk with
+// the tables of the geometry at 1/2^r size; its packets step (recut_cuts_gather_kernel) is still one workgroup per packet of
+// the master: the payload is copied as it is, the 28 header bytes are written per cut (recut_cut_header).  A call whose
+// reduces are all 0 takes the kernels above.
 #include "recut_core.hpp"
 
 #ifdef ICER_WAVE_EMU
@@ -24,7 +30,17 @@ struct icerx_recutter {
     // device tables, uploaded once: CRC-32 table, table slot of every unit and the D7 final order (Plan::units order), the
     // unit table itself (scan_ladder_wave reads cap_is_bound of the unit at the cut: 0 here)
     void *crc = nullptr, *unit_slot = nullptr, *final_order = nullptr, *units = nullptr;
+    // icerx_recutter_create_reduced: the same three tables for the geometry at 1/2^r size, r = 1 .. max_reduce, built by the
+    // planner on that geometry, and full_to_cut[u]: the unit there that unit u of the full geometry stands for (kNoPacket: none)
+    int max_reduce = 0;
+    struct Reduced {
+        uint32_t n_units = 0;
+        void *unit_slot = nullptr, *final_order = nullptr, *units = nullptr, *full_to_cut = nullptr;
+    } red[kRecutMaxReduce + 1];
+    uint32_t units_total = 0;                         // n_units + red[1 .. max_reduce].n_units
 };
+
+extern "C" void icerx_recutter_destroy(icerx_recutter *r);
 
 namespace {
 
@@ -36,11 +52,24 @@ constexpr uint32_t kRecutPlanThreads = 256, kRecutGatherThreads = 256;
 constexpr int kRecutMaxFrames = 65535;            // (frames are the y dimension of the gather's grid)
 
 struct RecutLayout {
-    size_t head, bitmap, gcount, scount, cands, tab_off, tab_bits, bits, foff, total;
+    size_t head, bitmap, gcount, scount, cands, tab_off, tab_bits, bits, foff, by_unit, total;
     uint32_t groups, supers;
 };
 
-RecutLayout recut_layout(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas)
+// the tables of every geometry and the cuts of a call, passed by value with the launches
+struct RecutCutTables {
+    const uint32_t *unit_slot[kRecutMaxReduce + 1], *final_order[kRecutMaxReduce + 1], *full_to_cut[kRecutMaxReduce + 1];
+    const UnitDesc *units[kRecutMaxReduce + 1];
+    uint32_t n_units[kRecutMaxReduce + 1], bits_at[kRecutMaxReduce + 1];     // bits_at: where a frame's bit counts at r start
+};
+struct RecutCuts {
+    uint64_t quota[kMaxLadder];
+    uint8_t reduce[kMaxLadder];
+};
+
+// cuts: the workspace of icerx_recut_device_cuts_async -- bit counts for every geometry, and each cut's final offsets twice,
+// in the order of its own geometry's units (by_unit) and in the order of the master's (foff); rows of n_units entries both
+RecutLayout recut_layout(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas, bool cuts = false)
 {
     RecutLayout L;
     const size_t N = (size_t)n, slots = r->geom.slots();
@@ -55,10 +84,58 @@ RecutLayout recut_layout(const icerx_recutter *r, int n, size_t data_bytes, int 
     L.cands = take(sizeof(DCandRec) * ((data_bytes + 1u) / 2u));     // (two preambles cannot overlap)
     L.tab_off = take(sizeof(uint32_t) * N * slots);
     L.tab_bits = take(sizeof(uint32_t) * N * slots);
-    L.bits = take(sizeof(uint32_t) * N * r->n_units);
+    L.bits = take(sizeof(uint32_t) * N * (cuts ? r->units_total : r->n_units));
     L.foff = take(sizeof(uint64_t) * N * r->n_units * (size_t)n_quotas);
+    L.by_unit = cuts ? take(sizeof(uint64_t) * N * r->n_units * (size_t)n_quotas) : at;
     L.total = at;
     return L;
+}
+
+// LDS of the walks: kPlanChunk DCand, the walk's result, two flags; for the cuts, kPlanChunk decomp_level bytes behind them
+constexpr uint32_t kRecutWalkLds = kPlanChunk * sizeof(DCand) + sizeof(DWalk) + 16u, kRecutWalkLevelsLds = kRecutWalkLds + kPlanChunk;
+
+// recut_plan_kernel's walk for the cuts (a body of its own, so that the byte-quota kernel stays as it was measured): the
+// decoder's cursor walk of the frame [off, off + len) into its packet table `to` / `tb`, by the whole workgroup -- the
+// threads summarise kPlanChunk candidates into LDS, thread 0 runs the cursor rule over them and notes a valid packet of
+// another image size.  Returns the frame's status (recut_frame_status), the same in every thread; *max_level is the
+// largest decomp_level of a packet the walk accepted (0: none).
+ICER_DEV int recut_walk_frame(uint8_t *lds, const uint8_t *blob, uint32_t blob_len, uint64_t off, uint64_t len, const DCandRec *recs,
+                              const AsyncHead *head, const DPlanGeom &geom, uint64_t image_w, uint64_t image_h, uint32_t *to, uint32_t *tb,
+                              uint32_t *max_level)
+{
+    DCand *chunk = reinterpret_cast<DCand *>(lds);
+    DWalk *shared_walk = reinterpret_cast<DWalk *>(lds + kPlanChunk * sizeof(DCand));
+    uint32_t *shared_other = reinterpret_cast<uint32_t *>(lds + kPlanChunk * sizeof(DCand) + sizeof(DWalk));
+    uint8_t *levels = lds + kRecutWalkLds;
+    const uint32_t tid = threadIdx.x;
+    const bool inside = off <= blob_len && len <= blob_len - off;
+    DWalk s;
+    dwalk_init(&s, image_w, image_h);
+    uint32_t other = 0, top = 0;
+    if (inside) {
+        const uint32_t nc = head->n_cands, first = dlower_bound(recs, nc, (uint32_t)off), last = dlower_bound(recs, nc, (uint32_t)(off + len));
+        for (uint32_t at = first; at < last; at += kPlanChunk) {
+            const uint32_t m = last - at < kPlanChunk ? last - at : kPlanChunk;
+            for (uint32_t t = tid; t < m; t += blockDim.x) {
+                chunk[t] = dplan_summary(geom, blob, (uint32_t)off, (uint32_t)len, recs[at + t]);
+                levels[t] = chunk[t].end != 0 ? blob[recs[at + t].off + 4u] : (uint8_t)0;
+            }
+            ICER_BARRIER();
+            if (tid == 0)
+                for (uint32_t t = 0; t < m; t++) {
+                    if (chunk[t].end != 0 && chunk[t].rel >= s.cursor) {
+                        if (chunk[t].w != image_w || chunk[t].h != image_h) other = 1;
+                        if (levels[t] > top) top = levels[t];
+                    }
+                    dplan_accept(&s, chunk[t], to, tb);
+                }
+            ICER_BARRIER();
+        }
+    }
+    if (tid == 0) { *shared_walk = s; shared_other[0] = other; shared_other[1] = top; }
+    ICER_BARRIER();
+    *max_level = shared_other[1];
+    return recut_frame_status(inside, shared_walk->cursor, shared_other[0] != 0u);
 }
 
 // one workgroup per frame (frame k addressed as in plan_frames_kernel).  The walk: the threads summarise kPlanChunk
@@ -116,6 +193,49 @@ recut_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uin
     }
 }
 
+// recut_plan_kernel for cuts: the packet table once per frame, then the bit counts of every geometry in use (bit r of
+// `used`) through that geometry's slot map, and wavefront v takes the cuts v, v + waves, ...: the walk with the tables of
+// the cut's geometry leaves the final offsets in the order of that geometry's units (by_unit; reduce 0: foff at once), and
+// the workgroup turns them into the order of the master's units, which the gather goes by.  Row c * n + k of sizes / rcs
+// and of foff / by_unit (n_units[0] entries a row).
+__global__ void __launch_bounds__(256)
+recut_cuts_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uint64_t *__restrict__ offsets, uint64_t stream_stride,
+                       const uint64_t *__restrict__ lens, const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head,
+                       DPlanGeom geom, uint64_t image_w, uint64_t image_h, RecutCutTables tabs, uint32_t units_total, RecutCuts cuts,
+                       uint32_t n_c, uint32_t used, uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits,
+                       uint32_t *__restrict__ unit_bits, uint64_t *__restrict__ foff, uint64_t *__restrict__ by_unit,
+                       unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs)
+{
+    ICER_DYNAMIC_LDS(uint8_t, lds);
+    const uint32_t k = blockIdx.x, n = gridDim.x, tid = threadIdx.x, n_full = tabs.n_units[0];
+    const uint64_t off = offsets ? offsets[k] : (uint64_t)k * stream_stride, len = lens[k];
+    uint32_t *to = tab_off + (size_t)k * geom.slots(), *tb = tab_bits + (size_t)k * geom.slots();
+    uint32_t *bits = unit_bits + (size_t)k * units_total;
+    uint32_t max_level = 0;
+    const int status = recut_walk_frame(lds, blob, blob_len, off, len, recs, head, geom, image_w, image_h, to, tb, &max_level);
+    for (uint32_t r = 0; r <= (uint32_t)kRecutMaxReduce; r++)
+        if (((used >> r) & 1u) && recut_cut_status(status, max_level, r) == kOk)
+            recut_unit_bits(to, tb, tabs.unit_slot[r], tabs.n_units[r], bits + tabs.bits_at[r], tid, blockDim.x);
+    ICER_BARRIER();
+#ifdef ICER_HOST_MOCK
+    const uint32_t wave = 0, waves = 1;
+#else
+    const uint32_t wave = tid >> 6, waves = blockDim.x >> 6;
+#endif
+    for (uint32_t c = wave; c < n_c; c += waves) {
+        const size_t row = (size_t)c * n + k;
+        const uint32_t r = cuts.reduce[c];
+        recut_scan_wave(recut_cut_status(status, max_level, r), bits + tabs.bits_at[r], tabs.final_order[r], tabs.n_units[r], cuts.quota[c],
+                        tabs.units[r], (r ? by_unit : foff) + row * n_full, sizes + row, rcs + row);
+    }
+    ICER_BARRIER();
+    for (uint32_t c = 0; c < n_c; c++) {
+        const size_t row = (size_t)c * n + k;
+        const uint32_t r = cuts.reduce[c];
+        if (r) recut_offsets_by_master_unit(by_unit + row * n_full, tabs.full_to_cut[r], n_full, foff + row * n_full, tid, blockDim.x);
+    }
+}
+
 // one workgroup per (unit, frame): the unit's packet, wherever it lies in the master, to every quota's stream that keeps it
 __global__ void __launch_bounds__(256)
 recut_gather_kernel(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets, uint64_t stream_stride, DPlanGeom geom,
@@ -135,6 +255,74 @@ recut_gather_kernel(const uint8_t *__restrict__ blob, const uint64_t *__restrict
     // (the walk accepted this packet: header and payload lie inside the frame, and the frame inside the blob)
     copy_unit_recut(blob + off + tab_off[(size_t)frame * geom.slots() + unit_slot[ui]], len, offs, off_pitch, n_q,
                     out + (size_t)frame * out_stride, (size_t)n * out_stride, threadIdx.x, blockDim.x);
+}
+
+// recut_gather_kernel for cuts, still one workgroup per (unit of the master, frame): the payload goes as it is to every cut
+// that keeps the packet, from byte 28 on; the header of cut c is written by thread c as it stands in the derived stream
+// at the cut's reduce (recut_cut_header), so no two threads write the same byte.
+__global__ void __launch_bounds__(256)
+recut_cuts_gather_kernel(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets, uint64_t stream_stride, DPlanGeom geom,
+                         const uint32_t *__restrict__ unit_slot, uint32_t n_units, const uint32_t *__restrict__ tab_off,
+                         const uint32_t *__restrict__ tab_bits, const uint64_t *__restrict__ foff, RecutCuts cuts, uint32_t n_c,
+                         const uint32_t *__restrict__ crc_tab, uint8_t *__restrict__ out, size_t out_stride)
+{
+    const uint32_t ui = blockIdx.x, frame = blockIdx.y, n = gridDim.y;
+    const size_t off_pitch = (size_t)n * n_units, q_pitch = (size_t)n * out_stride;
+    const uint64_t *offs = foff + (size_t)frame * n_units + ui;
+    bool any = false;
+    for (uint32_t c = 0; c < n_c; c++) any |= offs[(size_t)c * off_pitch] != ~0ull;
+    if (!any) return;
+    const uint64_t off = offsets ? offsets[frame] : (uint64_t)frame * stream_stride;
+    const size_t slot = (size_t)frame * geom.slots() + unit_slot[ui];
+    // (the walk accepted this packet: header and payload lie inside the frame, and the frame inside the blob)
+    const uint8_t *src = blob + off + tab_off[slot];
+    uint8_t *rows = out + (size_t)frame * out_stride;
+    for (uint32_t c = threadIdx.x; c < n_c; c += blockDim.x) {
+        const uint64_t at = offs[(size_t)c * off_pitch];
+        if (at != ~0ull) recut_cut_header(crc_tab, src, cuts.reduce[c], rows + (size_t)c * q_pitch + at);
+    }
+    copy_unit_recut(src + kHeaderBytes, (tab_bits[slot] + 7u) >> 3, offs, off_pitch, n_c, rows + kHeaderBytes, q_pitch, threadIdx.x, blockDim.x);
+}
+
+hipError_t recut_upload(void **p, const void *src, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    return e != hipSuccess ? e : hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice);
+}
+
+// step 1 of both calls: the candidates over the blob (decode_async's step 1), and every frame's packet table emptied
+int recut_blob_pass(const icerx_recutter *r, const RecutLayout &L, uint8_t *ws, int n, const uint8_t *d_data, size_t data_bytes, hipStream_t st)
+{
+    int rc = ICER_RESULT_OK;
+    AsyncHead *head = (AsyncHead *)(ws + L.head);
+    DCandRec *recs = (DCandRec *)(ws + L.cands);
+    const uint32_t *crc_tab = (const uint32_t *)r->crc;
+    const uint32_t blob_len = (uint32_t)data_bytes;
+#ifdef ICER_HOST_MOCK
+    const uint32_t cus = kGridCus;
+#else
+    const uint32_t cus = (uint32_t)r->n_cus;
+#endif
+    auto grid = [](size_t items, size_t per_block, size_t cap) { return (unsigned)std::max<size_t>(1, std::min((items + per_block - 1) / per_block, cap)); };
+    HIP_TRY(hipMemsetAsync(head, 0, sizeof(AsyncHead), st));
+    HIP_TRY(hipMemsetAsync(ws + L.tab_off, 0xFF, sizeof(uint32_t) * (size_t)n * r->geom.slots(), st));          // (kNoPacket)
+    if (L.groups) {
+        ICER_LAUNCH_ON(st, mark_headers_kernel, (L.groups + 255u) / 256u, 256, 0, d_data, blob_len, crc_tab, (uint32_t *)(ws + L.bitmap),
+                       (uint32_t *)(ws + L.gcount), L.groups);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, scan_groups_kernel, (L.supers + 255u) / 256u, 256, 0, (uint32_t *)(ws + L.gcount), L.groups,
+                       (uint32_t *)(ws + L.scount), L.supers);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, scan_supers_kernel, 1, 64, 0, (uint32_t *)(ws + L.scount), L.supers, head);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, compact_headers_kernel, (L.groups + 255u) / 256u, 256, 0, (const uint32_t *)(ws + L.bitmap),
+                       (const uint32_t *)(ws + L.gcount), (const uint32_t *)(ws + L.scount), L.groups, recs);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, payload_crcs_kernel, grid((data_bytes + 1u) / 2u, 4, 8u * cus), 256, 0, d_data, blob_len, crc_tab, recs, head);
+        HIP_TRY(hipGetLastError());
+    }
+done:
+    return rc;
 }
 
 int recut_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
@@ -157,35 +345,12 @@ int recut_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t data_byt
     DCandRec *recs = (DCandRec *)(ws + L.cands);
     uint32_t *tab_off = (uint32_t *)(ws + L.tab_off), *tab_bits = (uint32_t *)(ws + L.tab_bits), *bits = (uint32_t *)(ws + L.bits);
     uint64_t *foff = (uint64_t *)(ws + L.foff);
-    const uint32_t *crc_tab = (const uint32_t *)r->crc;
     const uint32_t blob_len = (uint32_t)data_bytes;
-#ifdef ICER_HOST_MOCK
-    const uint32_t cus = kGridCus;
-#else
-    const uint32_t cus = (uint32_t)r->n_cus;
-#endif
-    auto grid = [](size_t items, size_t per_block, size_t cap) { return (unsigned)std::max<size_t>(1, std::min((items + per_block - 1) / per_block, cap)); };
 
-    // 1. candidates over the blob (decode_async's step 1)
-    HIP_TRY(hipMemsetAsync(head, 0, sizeof(AsyncHead), st));
-    HIP_TRY(hipMemsetAsync(tab_off, 0xFF, sizeof(uint32_t) * (size_t)n * r->geom.slots(), st));          // (kNoPacket)
-    if (L.groups) {
-        ICER_LAUNCH_ON(st, mark_headers_kernel, (L.groups + 255u) / 256u, 256, 0, d_data, blob_len, crc_tab, (uint32_t *)(ws + L.bitmap),
-                       (uint32_t *)(ws + L.gcount), L.groups);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, scan_groups_kernel, (L.supers + 255u) / 256u, 256, 0, (uint32_t *)(ws + L.gcount), L.groups,
-                       (uint32_t *)(ws + L.scount), L.supers);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, scan_supers_kernel, 1, 64, 0, (uint32_t *)(ws + L.scount), L.supers, head);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, compact_headers_kernel, (L.groups + 255u) / 256u, 256, 0, (const uint32_t *)(ws + L.bitmap),
-                       (const uint32_t *)(ws + L.gcount), (const uint32_t *)(ws + L.scount), L.groups, recs);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, payload_crcs_kernel, grid((data_bytes + 1u) / 2u, 4, 8u * cus), 256, 0, d_data, blob_len, crc_tab, recs, head);
-        HIP_TRY(hipGetLastError());
-    }
+    // 1. candidates over the blob
+    if ((rc = recut_blob_pass(r, L, ws, n, d_data, data_bytes, st)) != ICER_RESULT_OK) return rc;
     // 2. per frame: packet table, unit bit counts, the quota walk at every quota
-    ICER_LAUNCH_ON(st, recut_plan_kernel, (unsigned)n, kRecutPlanThreads, kPlanChunk * sizeof(DCand) + sizeof(DWalk) + 16u, d_data, blob_len,
+    ICER_LAUNCH_ON(st, recut_plan_kernel, (unsigned)n, kRecutPlanThreads, kRecutWalkLds, d_data, blob_len,
                    d_offsets, (uint64_t)stream_stride, d_lens, recs, head, r->geom, r->w, r->h, (const uint32_t *)r->unit_slot,
                    (const uint32_t *)r->final_order, (const UnitDesc *)r->units, r->n_units, lq, (uint32_t)n_quotas, tab_off, tab_bits,
                    bits, foff, (unsigned long long *)d_sizes, d_rcs);
@@ -198,28 +363,95 @@ done:
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-void icerx_recutter_destroy(icerx_recutter *r)
+int recut_cuts_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
+                     const uint64_t *d_lens, const int *reduces, const size_t *quotas, int n_cuts, uint8_t *d_out, size_t out_stride,
+                     uint64_t *d_sizes, int32_t *d_rcs, void *workspace, size_t workspace_bytes, hipStream_t st)
 {
-    if (!r) return;
-    for (void *p : {r->crc, r->unit_slot, r->final_order, r->units})
-        if (p) (void)hipFree(p);
-    delete r;
+    g_error.clear();
+    if (!r || n < 1 || n > kRecutMaxFrames || n_cuts < 1 || n_cuts > kMaxLadder) return ICER_INVALID_INPUT;
+    if (!reduces || !quotas || !d_lens || !d_out || !d_sizes || !d_rcs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
+    RecutCuts cuts = {};
+    size_t top = 0;
+    uint32_t used = 0;
+    for (int c = 0; c < n_cuts; c++) {
+        if (reduces[c] < 0 || reduces[c] > r->max_reduce) return ICER_INVALID_INPUT;
+        cuts.quota[c] = quotas[c]; cuts.reduce[c] = (uint8_t)reduces[c];
+        used |= 1u << reduces[c];
+        top = std::max(top, quotas[c]);
+    }
+    if (out_stride < top) return ICER_INVALID_INPUT;
+    if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
+    const RecutLayout L = recut_layout(r, n, data_bytes, n_cuts, true);
+    if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
+    // (every reduce 0: the byte-quota re-cut itself, whose workspace is a part of this one's)
+    if (used == 1u)
+        return recut_async(r, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, quotas, n_cuts, d_out, out_stride, d_sizes, d_rcs,
+                           workspace, workspace_bytes, st);
+    int rc = ICER_RESULT_OK;
+    uint8_t *ws = (uint8_t *)workspace;
+    uint32_t *tab_off = (uint32_t *)(ws + L.tab_off), *tab_bits = (uint32_t *)(ws + L.tab_bits);
+    uint64_t *foff = (uint64_t *)(ws + L.foff);
+    RecutCutTables tabs = {};
+    uint32_t at = 0;
+    for (int k = 0; k <= r->max_reduce; k++) {
+        const icerx_recutter::Reduced &g = r->red[k];
+        tabs.unit_slot[k] = (const uint32_t *)g.unit_slot; tabs.final_order[k] = (const uint32_t *)g.final_order;
+        tabs.full_to_cut[k] = (const uint32_t *)g.full_to_cut; tabs.units[k] = (const UnitDesc *)g.units;
+        tabs.n_units[k] = g.n_units; tabs.bits_at[k] = at;
+        at += g.n_units;
+    }
+
+    // 1. candidates over the blob
+    if ((rc = recut_blob_pass(r, L, ws, n, d_data, data_bytes, st)) != ICER_RESULT_OK) return rc;
+    // 2. per frame: packet table, then every cut's walk with the tables of its geometry
+    ICER_LAUNCH_ON(st, recut_cuts_plan_kernel, (unsigned)n, kRecutPlanThreads, kRecutWalkLevelsLds, d_data, (uint32_t)data_bytes, d_offsets,
+                   (uint64_t)stream_stride, d_lens, (const DCandRec *)(ws + L.cands), (const AsyncHead *)(ws + L.head), r->geom, r->w, r->h,
+                   tabs, r->units_total, cuts, (uint32_t)n_cuts, used, tab_off, tab_bits, (uint32_t *)(ws + L.bits), foff,
+                   (uint64_t *)(ws + L.by_unit), (unsigned long long *)d_sizes, d_rcs);
+    HIP_TRY(hipGetLastError());
+    // 3. the kept packets, each with its cut's header
+    ICER_LAUNCH_ON(st, recut_cuts_gather_kernel, dim3(r->n_units, (unsigned)n), kRecutGatherThreads, 0, d_data, d_offsets,
+                   (uint64_t)stream_stride, r->geom, (const uint32_t *)r->unit_slot, r->n_units, tab_off, tab_bits, foff, cuts,
+                   (uint32_t)n_cuts, (const uint32_t *)r->crc, d_out, out_stride);
+    HIP_TRY(hipGetLastError());
+done:
+    return rc;
 }
 
-int icerx_recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments,
-                          int sample_bits)
+// the three tables of a plan on the device; slot[u]: the slot of unit u in the packet table of `geom`, levels raised by `reduce`
+int recut_upload_plan(const Plan &plan, const DPlanGeom &geom, uint32_t reduce, std::vector<uint32_t> *slot, void **unit_slot,
+                      void **final_order, void **units)
+{
+    int rc = ICER_RESULT_OK;
+    slot->resize(plan.units.size());
+    for (size_t u = 0; u < plan.units.size(); u++) {
+        const UnitDesc &d = plan.units[u];
+        (*slot)[u] = geom.slot(d.chan, d.level + reduce, d.subband, d.seg, d.lsb);
+    }
+    HIP_TRY(recut_upload(unit_slot, slot->data(), sizeof(uint32_t) * slot->size()));
+    HIP_TRY(recut_upload(final_order, plan.final_order.data(), sizeof(uint32_t) * plan.final_order.size()));
+    HIP_TRY(recut_upload(units, plan.units.data(), sizeof(UnitDesc) * plan.units.size()));
+done:
+    return rc;
+}
+
+int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments, int sample_bits,
+                    int max_reduce)
 {
     g_error.clear();
     if (!out) return ICER_INVALID_INPUT;
     *out = nullptr;
     if (sample_bits != 8 && sample_bits != 16) return ICER_INVALID_INPUT;
-    Plan plan;
-    const int prc = build_plan(&plan, w, h, channels, stages, segments > (unsigned)kMaxSegments ? kMaxSegments + 1 : (int)segments, sample_bits);
+    const int segs = segments > (unsigned)kMaxSegments ? kMaxSegments + 1 : (int)segments;
+    std::vector<Plan> plans(1);
+    const int prc = build_plan(&plans[0], w, h, channels, stages, segs, sample_bits);
     if (prc != kOk) return prc;
+    if (max_reduce < 0 || max_reduce >= stages) return ICER_INVALID_INPUT;
+    plans.resize((size_t)max_reduce + 1);
+    for (int k = 1; k <= max_reduce; k++) {
+        const int krc = build_plan(&plans[k], (size_t)reduced_dim(w, k), (size_t)reduced_dim(h, k), channels, stages - k, segs, sample_bits);
+        if (krc != kOk) return krc;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no usable HIP device");
 #ifndef ICER_HOST_MOCK
@@ -229,34 +461,65 @@ int icerx_recutter_create(icerx_recutter **out, int device, size_t w, size_t h, 
     }
 #endif
     icerx_recutter *r = new icerx_recutter;
-    r->device = device; r->w = w; r->h = h;
+    r->device = device; r->w = w; r->h = h; r->max_reduce = max_reduce;
     r->geom = DPlanGeom{(uint32_t)channels, (uint32_t)stages, segments, (uint32_t)(sample_bits == 8 ? kPlanes8 : kPlanes)};
-    r->n_units = (uint32_t)plan.units.size();
+    r->n_units = (uint32_t)plans[0].units.size();
 #ifndef ICER_HOST_MOCK
     { int cur = 0; hipDeviceProp_t prop; if (hipGetDevice(&cur) == hipSuccess && hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) r->n_cus = prop.multiProcessorCount; }
 #endif
     uint32_t crc_tab[256];
     build_crc32_table(crc_tab);
-    std::vector<uint32_t> slot(plan.units.size());
-    for (size_t u = 0; u < plan.units.size(); u++) {
-        const UnitDesc &d = plan.units[u];
-        slot[u] = r->geom.slot(d.chan, d.level, d.subband, d.seg, d.lsb);
-    }
     int rc = ICER_RESULT_OK;
-    auto upload = [](void **p, const void *src, size_t bytes) {
-        const hipError_t e = hipMalloc(p, bytes);
-        return e != hipSuccess ? e : hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice);
-    };
-    HIP_TRY(upload(&r->crc, crc_tab, sizeof crc_tab));
-    HIP_TRY(upload(&r->unit_slot, slot.data(), sizeof(uint32_t) * slot.size()));
-    HIP_TRY(upload(&r->final_order, plan.final_order.data(), sizeof(uint32_t) * plan.final_order.size()));
-    HIP_TRY(upload(&r->units, plan.units.data(), sizeof(UnitDesc) * plan.units.size()));
+    std::vector<uint32_t> slot0, slot;
+    HIP_TRY(recut_upload(&r->crc, crc_tab, sizeof crc_tab));
+    if ((rc = recut_upload_plan(plans[0], r->geom, 0, &slot0, &r->unit_slot, &r->final_order, &r->units)) != ICER_RESULT_OK) goto done;
+    r->red[0].n_units = r->n_units; r->red[0].unit_slot = r->unit_slot; r->red[0].final_order = r->final_order; r->red[0].units = r->units;
+    r->units_total = r->n_units;
+    for (int k = 1; k <= max_reduce; k++) {
+        icerx_recutter::Reduced &g = r->red[k];
+        g.n_units = (uint32_t)plans[k].units.size();
+        r->units_total += g.n_units;
+        if ((rc = recut_upload_plan(plans[k], r->geom, (uint32_t)k, &slot, &g.unit_slot, &g.final_order, &g.units)) != ICER_RESULT_OK) goto done;
+        std::vector<uint32_t> of_slot(r->geom.slots(), kNoPacket), full_to_cut(slot0.size());
+        for (size_t u = 0; u < slot.size(); u++) of_slot[slot[u]] = (uint32_t)u;
+        for (size_t u = 0; u < slot0.size(); u++) full_to_cut[u] = of_slot[slot0[u]];
+        HIP_TRY(recut_upload(&g.full_to_cut, full_to_cut.data(), sizeof(uint32_t) * full_to_cut.size()));
+    }
     *out = r;
     return ICER_RESULT_OK;
 done:
     icerx_recutter_destroy(r);
     return rc;
 }
+
+}  // namespace
+
+extern "C" {
+
+void icerx_recutter_destroy(icerx_recutter *r)
+{
+    if (!r) return;
+    for (void *p : {r->crc, r->unit_slot, r->final_order, r->units})
+        if (p) (void)hipFree(p);
+    for (int k = 1; k <= kRecutMaxReduce; k++)
+        for (void *p : {r->red[k].unit_slot, r->red[k].final_order, r->red[k].units, r->red[k].full_to_cut})
+            if (p) (void)hipFree(p);
+    delete r;
+}
+
+int icerx_recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments,
+                          int sample_bits)
+{
+    return recutter_create(out, device, w, h, channels, stages, segments, sample_bits, 0);
+}
+
+int icerx_recutter_create_reduced(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments,
+                                  int sample_bits, int max_reduce)
+{
+    return recutter_create(out, device, w, h, channels, stages, segments, sample_bits, max_reduce);
+}
+
+int icerx_recutter_max_reduce(const icerx_recutter *r) { return r ? r->max_reduce : 0; }
 
 size_t icerx_recut_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas)
 {
@@ -270,6 +533,21 @@ int icerx_recut_device_async(icerx_recutter *r, int n, const void *d_data, size_
 {
     return recut_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, quotas, n_quotas, d_out, out_stride,
                        d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t icerx_recut_cuts_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts)
+{
+    if (!r || n <= 0 || n_cuts < 1 || n_cuts > kMaxLadder) return 0;
+    return recut_layout(r, n, data_bytes, n_cuts, true).total;
+}
+
+int icerx_recut_device_cuts_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                  size_t stream_stride, const uint64_t *d_lens, const int *reduces, const size_t *quotas, int n_cuts,
+                                  uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *d_workspace,
+                                  size_t workspace_bytes, void *stream)
+{
+    return recut_cuts_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, reduces, quotas, n_cuts, d_out,
+                            out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

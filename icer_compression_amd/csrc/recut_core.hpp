@@ -10,10 +10,15 @@
 //                      kUnitTooBig ("does not fit"), so the walk ends there
 //   recut_scan_wave    one frame at one quota: scan_ladder_wave, or the frame's error (no offsets, size 0)
 //   copy_unit_recut    copy_unit_ladder for a source of any byte alignment (a packet inside a stored stream)
+// and, for cuts by resolution as well (icerx_recut_device_cuts_async), at the end of this file:
+//   recut_cut_status   a frame's status at reduce r
+//   recut_cut_header   a kept packet's header as it stands in the derived stream at reduce r
+//   recut_offsets_by_master_unit   a cut's final offsets, from its geometry's unit order to the master's
 // Written with the SPMD macros of wave.hpp, so that tests/emu/recut_emu.cpp runs the same source on a CPU.
 #pragma once
 #include "assemble_ladder.hpp"
 #include "decoder_core.hpp"
+#include "decoder_plan.hpp"
 
 namespace icer {
 
@@ -85,6 +90,53 @@ ICER_DEV void copy_unit_recut(const uint8_t *src, uint32_t len, const uint64_t *
             if (shift && i + 1u >= nfull) continue;
             reinterpret_cast<uint32_t *>(dst + sa + shift)[i] = shift ? (lo >> (8u * shift)) | (hi << (32u - 8u * shift)) : lo;
         }
+    }
+}
+
+// ---- cuts by resolution as well as by byte quota (icerx_recut_device_cuts_async) --------------------------------------
+// A cut (reduce r, quota Q) of a master M is the re-cut at Q of its derived stream M_r (include/icer_hip_dec.h): M's packet
+// table is read through the unit -> slot map of the geometry at 1/2^r size, whose unit (ch, lv, sb, sg, lsb) is M's slot
+// (ch, lv + r, sb, sg, lsb), and a kept packet gets the header it has in M_r.
+constexpr int kRecutMaxReduce = kMaxStages - 1;
+
+// a frame's status at reduce r: the master's own, and at r > 0 no stream when no valid packet lies above level r
+ICER_HD int recut_cut_status(int status, uint32_t max_level, uint32_t reduce)
+{
+    if (status != kOk || reduce == 0u) return status;
+    return max_level <= reduce ? kDecoderOutOfData : kOk;
+}
+
+// the 28 header bytes at `src` as they stand in the derived stream at reduce r -> dst: decomp_level - r, image_w and image_h
+// ceil(. / 2^r), the header CRC over the 24 bytes before it; r = 0: a copy.  Any alignment on both sides, one thread.
+ICER_HD void recut_cut_header(const uint32_t *crc_tab, const uint8_t *src, uint32_t reduce, uint8_t *dst)
+{
+    if (reduce == 0u) {
+        for (uint32_t j = 0; j < (uint32_t)kHeaderBytes; j++) dst[j] = src[j];
+        return;
+    }
+    const uint32_t w = (uint32_t)reduced_dim(load_le32(src + 8), (int)reduce), h = (uint32_t)reduced_dim(load_le32(src + 12), (int)reduce);
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < 24u; j++) {
+        uint8_t b = src[j];
+        if (j == 4u) b = (uint8_t)(b - reduce);
+        else if (j >= 8u && j < 12u) b = (uint8_t)(w >> (8u * (j - 8u)));
+        else if (j >= 12u && j < 16u) b = (uint8_t)(h >> (8u * (j - 12u)));
+        dst[j] = b;
+        c = crc_tab[(c ^ b) & 255u] ^ (c >> 8);
+    }
+    c ^= 0xFFFFFFFFu;
+    for (uint32_t j = 0; j < 4u; j++) dst[24u + j] = (uint8_t)(c >> (8u * j));
+}
+
+// final offsets of one frame at one cut, from the order of the geometry at 1/2^r size (`by_unit`, what the quota walk
+// leaves) to the order of the master's units: full_to_cut[u] is the unit of that geometry that master unit u stands for,
+// kNoPacket for a unit of a level the cut leaves out.  Thread `tid` of `nth`.
+ICER_HD void recut_offsets_by_master_unit(const uint64_t *by_unit, const uint32_t *full_to_cut, uint32_t n_full, uint64_t *by_master,
+                                          uint32_t tid, uint32_t nth)
+{
+    for (uint32_t u = tid; u < n_full; u += nth) {
+        const uint32_t v = full_to_cut[u];
+        by_master[u] = v == kNoPacket ? ~0ull : by_unit[v];
     }
 }
 

@@ -57,6 +57,15 @@ def bind(path: str) -> C.CDLL:
         lib.icerx_reduced_size.argtypes = [_sz, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz)]
         lib.icerx_reduced_size.restype = None
         lib.icerx_decompress_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int] + tail + [C.c_int, C.c_int]
+    # re-cutting by resolution as well as by byte quota
+    if hasattr(lib, "icerx_recut_device_cuts_async"):
+        lib.icerx_recutter_create_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int, _sz, _sz, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
+        lib.icerx_recutter_max_reduce.argtypes = [C.c_void_p]
+        lib.icerx_recut_cuts_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, C.c_int]
+        lib.icerx_recut_cuts_workspace_bytes.restype = _sz
+        lib.icerx_recut_device_cuts_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_int),
+                                                      C.POINTER(_sz), C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
+                                                      C.c_void_p]
     return lib
 
 
@@ -361,9 +370,14 @@ class Recutter:
     """Stored streams re-cut to smaller byte quotas on the device, without the pixels and without re-coding
     (icerx_recutter_* / icerx_recut_device_async, include/icer_hip_dec.h): from a master of a frame made at quota Qm, the
     stream the encoder makes at any quota Q <= Qm (any Q for a complete master), byte for byte.  One recutter per geometry
-    the masters were made with."""
+    the masters were made with.
 
-    def __init__(self, w: int, h: int, channels: int, stages: int, segments: int, bits: int = 16, device: int = -1, lib=None):
+    max_reduce = R > 0 (icerx_recutter_create_reduced): the recutter also cuts by resolution -- recut_cuts_torch / recut_cuts
+    take cuts (reduce r, quota) with r in 0 .. R and give, from the same masters, streams of the image at 1/2^r size that
+    any decoder made for stages - r decodes (the re-cut of the master's derived stream, include/icer_hip_dec.h)."""
+
+    def __init__(self, w: int, h: int, channels: int, stages: int, segments: int, bits: int = 16, device: int = -1, lib=None,
+                 max_reduce: int = 0):
         self.lib = lib or load_library()
         if not hasattr(self.lib, "icerx_recut_device_async"):
             raise RuntimeError("this build of the decoder library has no icerx_recut_device_async")
@@ -377,7 +391,16 @@ class Recutter:
         L.icerx_recut_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.POINTER(_sz),
                                                C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
         self._workspaces = {}                # recut_torch: one cached workspace per torch stream
+        self._cuts_workspaces = {}           # recut_cuts_torch: the same, sized for the cuts call
         self.handle = C.c_void_p()
+        self.max_reduce = 0
+        if max_reduce != 0:
+            fn = _need(L, "icerx_recutter_create_reduced")
+            rc = fn(C.byref(self.handle), device, w, h, channels, stages, segments, bits, max_reduce)
+            if rc != 0:
+                raise RuntimeError(f"icerx_recutter_create_reduced: {rc} {L.icerx_decoder_last_error().decode()}")
+            self.max_reduce = int(L.icerx_recutter_max_reduce(self.handle))
+            return
         rc = L.icerx_recutter_create(C.byref(self.handle), device, w, h, channels, stages, segments, bits)
         if rc != 0:
             raise RuntimeError(f"icerx_recutter_create: {rc} {L.icerx_decoder_last_error().decode()}")
@@ -386,6 +409,8 @@ class Recutter:
         if self.handle:
             self.lib.icerx_recutter_destroy(self.handle)
             self.handle = C.c_void_p()
+        self._workspaces.clear()
+        self._cuts_workspaces.clear()
 
     def __del__(self):
         try:
@@ -462,6 +487,75 @@ class Recutter:
         torch.cuda.current_stream(dev).synchronize()
         out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
         return [[(int(rcs[q * n + f]), out[q * n + f, : int(sizes[q * n + f])].tobytes()) for f in range(n)] for q in range(Q)]
+
+    # ---- cuts by resolution as well as by byte quota (icerx_recut_device_cuts_async) ----
+    def cuts_workspace_bytes(self, n: int, data_bytes: int, n_cuts: int) -> int:
+        """icerx_recut_cuts_workspace_bytes: the device workspace one recut_cuts_device_async_ptrs call needs"""
+        return int(_need(self.lib, "icerx_recut_cuts_workspace_bytes")(self.handle, n, data_bytes, n_cuts))
+
+    def recut_cuts_device_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, reduces,
+                                     quotas, d_out: int, out_stride: int, d_sizes: int, d_rcs: int, d_workspace: int,
+                                     workspace_bytes: int, stream: int = 0, n_cuts=None) -> int:
+        """icerx_recut_device_cuts_async on raw device pointers (arguments as recut_device_async_ptrs; reduces and quotas: host
+        sequences of one length, None for a null pointer).  Frame f at cut c is row c * n + f of d_out and entry c * n + f of
+        d_sizes / d_rcs.  Enqueues on `stream` and returns the call's rc without waiting."""
+        fn = _need(self.lib, "icerx_recut_device_cuts_async")
+        red = None if reduces is None else (C.c_int * max(len(reduces), 1))(*[int(r) for r in reduces])
+        arr = None if quotas is None else (_sz * max(len(quotas), 1))(*[int(q) for q in quotas])
+        nc = n_cuts if n_cuts is not None else (len(quotas) if quotas is not None else 0)
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, red, arr, nc, d_out, out_stride, d_sizes, d_rcs,
+                  d_workspace, workspace_bytes, stream)
+
+    def recut_cuts_torch(self, data, lens, cuts, out, sizes, rcs, offsets=None, stream_stride=None) -> None:
+        """recut_torch with cuts = [(reduce, quota), ...] in place of the quotas: row and entry c * n + f hold frame f at cuts[c],
+        a stream of the image at 1/2^reduce size, so out[c] / sizes[c] go into decode_torch of a Decoder made for
+        stages - reduce as they are.  Everything else as recut_torch; the workspace is cached per stream, apart from
+        recut_torch's."""
+        import torch
+        n, Q = int(lens.shape[0]), len(cuts)
+        if offsets is None and stream_stride is None:
+            if data.dim() != 2:
+                raise ValueError("a 1-D blob needs offsets or stream_stride")
+            stream_stride = data.stride(0)
+        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8),
+                            ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32)) + \
+                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
+                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or sizes.numel() != Q * n or rcs.numel() != Q * n:
+            raise ValueError("out must be (Q * n, out_stride), sizes and rcs Q * n entries")
+        st = torch.cuda.current_stream(data.device)
+        need = self.cuts_workspace_bytes(n, data.numel(), Q)
+        work = self._cuts_workspaces.get(st.cuda_stream)
+        if work is None or work.numel() < max(need, 1):
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
+            self._cuts_workspaces[st.cuda_stream] = work
+        work.record_stream(st)
+        rc = self.recut_cuts_device_async_ptrs(n, data.data_ptr(), data.numel(), offsets.data_ptr() if offsets is not None else None,
+                                               int(stream_stride or 0), lens.data_ptr(), [c[0] for c in cuts], [c[1] for c in cuts],
+                                               out.data_ptr(), out.shape[-1], sizes.data_ptr(), rcs.data_ptr(), work.data_ptr(),
+                                               work.numel(), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_recut_device_cuts_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+
+    def recut_cuts(self, streams, cuts):
+        """bytes in, bytes out: res[c][f] = (rc, stream) of master streams[f] at cuts[c] = (reduce, quota) (copies to the device
+        and back, and waits: a convenience, not the fast path)"""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n, Q = len(streams), len(cuts)
+        lens = [len(s) for s in streams]
+        blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        stride = max(max(int(q) for _, q in cuts), 1)
+        out = torch.zeros((Q * n, stride), dtype=torch.uint8, device=dev)
+        sizes = torch.zeros(Q * n, dtype=torch.int64, device=dev)
+        rcs = torch.zeros(Q * n, dtype=torch.int32, device=dev)
+        self.recut_cuts_torch(torch.from_numpy(blob).to(dev), torch.tensor(lens, dtype=torch.int64, device=dev), cuts, out, sizes, rcs,
+                              offsets=torch.from_numpy(offs).to(dev))
+        torch.cuda.current_stream(dev).synchronize()
+        out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
+        return [[(int(rcs[c * n + f]), out[c * n + f, : int(sizes[c * n + f])].tobytes()) for f in range(n)] for c in range(Q)]
 
 
 # ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------

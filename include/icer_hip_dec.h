@@ -234,6 +234,62 @@ int icerx_recut_device_async(icerx_recutter *r, int n, const void *d_data, size_
                              uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs,
                              void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Re-cutting by resolution as well as by byte quota ---------------------------------------------------------------
+ * A stored master also holds the stream of the image at 1/2^r size: its derived stream M_r ("Decoding at 1/2^r resolution"
+ * above), which an unmodified lib_icer decoder told stages - r decodes.  A CUT is a pair (reduce r, byte quota Q) with
+ * 0 <= r <= max_reduce < stages, and the cut of a master M is DEFINED as
+ *     the output of the re-cut rule above at quota Q, applied to M_r, by a recutter made for
+ *     (ceil(w / 2^r), ceil(h / 2^r), channels, stages - r, segments, sample_bits).
+ * The same rule from the master's side: walk M with the decoder's cursor rule (every CRC-valid packet takes part, the last
+ * packet of a kind wins); packets of decomp_level <= r are stepped over and otherwise ignored; a packet of level l > r
+ * stands for the coding unit (channel, l - r, subband, bit plane, segment) of the geometry at 1/2^r size -- its segment
+ * grids are those of level l of the full geometry, as shown above -- while the priority order, the final order and the
+ * quota walk are that geometry's own (the planner run on it; the priority order of one geometry is not a part of
+ * another's); a unit without a packet ends the walk; the kept packets are copied in final order with decomp_level -= r,
+ * image_w = ceil(image_w / 2^r), image_h = ceil(image_h / 2^r) and the header CRC (bytes 24..27) recomputed over bytes
+ * 0..23; payload and payload CRC are copied verbatim.  Consequences:
+ *   - r = 0 is the re-cut above, byte for byte.
+ *   - a complete, undamaged master and Q above the length of M_r: the output is M_r itself with ICER_RESULT_OK.  (At Q equal
+ *     to that length the quota walk can drop the last unit -- floor(bits / 8) < Q - used - 28 is strict -- as an encode at
+ *     that quota does.)
+ *   - damage at a level <= r changes nothing in a cut at r; damage or truncation above level r cuts the stream at the first
+ *     unit, in the priority order of the geometry at 1/2^r size, that lost its packet.
+ *   - a master whose valid packets all have level <= r gives ICER_DECODER_OUT_OF_DATA and size 0 for that cut, as an empty
+ *     master does.
+ *   - the two per-frame checks are the MASTER's, the one place where the rule is stated on M and not on M_r: a frame that
+ *     leaves the blob, or that holds a valid packet of ANY level whose width or height is not the recutter's w / h, gives
+ *     ICER_INVALID_INPUT and size 0 for every cut -- also where M_r would not hold that packet, or would hold it with the
+ *     size of the geometry at 1/2^r.
+ *   - cuts compose: a stored output of cut (r, Q1), re-cut by a plain recutter of the geometry at 1/2^r size to Q2 <= Q1,
+ *     is cut (r, Q2) of the master.
+ * icerx_recutter_create_reduced makes a recutter with the tables of reduce 0 .. max_reduce (the unit table, the unit ->
+ * packet-table slot map and the final order of every geometry, from the planner on that geometry, uploaded once);
+ * 0 <= max_reduce < stages, else ICER_INVALID_INPUT; otherwise it refuses what icerx_recutter_create refuses, and where both
+ * the geometry and max_reduce are bad the geometry's code is returned (the planner runs on the full geometry first).  (The units of
+ * a geometry at 1/2^r size are a part of the full geometry's, so the planner accepts it whenever it accepts the full one.)
+ * icerx_recutter_create is max_reduce 0; every recutter serves icerx_recut_device_async unchanged. */
+int icerx_recutter_create_reduced(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages,
+                                  unsigned segments, int sample_bits, int max_reduce);
+int icerx_recutter_max_reduce(const icerx_recutter *r);            /* 0 for NULL or a plain recutter */
+
+/* icerx_recut_device_async with cuts in place of quotas, and with every stream-ordered promise of it: the call only
+ * enqueues.  `reduces` and `quotas` are HOST arrays of n_cuts entries, 1 .. ICERX_MAX_LADDER, in any order, repeats allowed,
+ * passed by value with the launch.  Frame f at cut c is row c * n + f of d_out, its size and return code d_sizes[c * n + f]
+ * / d_rcs[c * n + f] (the table of icerx_recut_device_async, per frame and cut); the block of n rows of one cut feeds
+ * icerx_decode_device_async of a decoder made for stages - reduces[c] directly.  Nothing is written behind a stream in its
+ * row, beyond the n_cuts * n rows, or to the masters.  The whole call returns ICER_INVALID_INPUT -- nothing enqueued, nothing
+ * written -- for what icerx_recut_device_async refuses, a null `reduces`, a reduce outside 0 .. max_reduce or a workspace
+ * smaller than icerx_recut_cuts_workspace_bytes(r, n, data_bytes, n_cuts) (which is never below
+ * icerx_recut_workspace_bytes of the same arguments: 4 more bytes per frame and coding unit of every geometry, 8 more per
+ * frame, cut and coding unit of the full geometry); ICER_FATAL_ERROR as there.  The packet table is made once per frame;
+ * a packet's payload is read once for all cuts that keep it.  A call whose reduces are all 0 runs icerx_recut_device_async's
+ * own kernels. */
+size_t icerx_recut_cuts_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts);
+int icerx_recut_device_cuts_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                  size_t stream_stride, const uint64_t *d_lens, const int *reduces, const size_t *quotas,
+                                  int n_cuts, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs,
+                                  void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* last error message of this thread's most recent failing call ("" if none) */
 const char *icerx_decoder_last_error(void);
 
