@@ -4,15 +4,16 @@
 //
 //   blob       candidates over the whole blob: a bitmap of header candidates (one thread per 256 bytes), a scan of its
 //              counts (per 256 groups, then one thread over those), the candidates compacted in offset order, their payload
-//              CRCs (one wavefront per candidate, grid-stride over the device count)
-//   frames     plan_kernel, one workgroup per frame: the cursor walk (decoder_dplan.hpp), the frame's rc / size / FrameInfo,
-//              its chains in fixed slots
+//              CRCs (one wavefront per candidate, grid-stride over the device count).  enqueue_blob_stage, over a BlobLayout
+//   frames     plan_frames_kernel, one workgroup per frame: the cursor walk (walk_frame, with decoder_dplan.hpp), the frame's
+//              rc / size / FrameInfo, its chains in fixed slots
 //   routing    every chain slot counted by (kernel, area bucket) for both answers of the by-load rule, the rule decided on
 //              the device, then each chain placed in its kernel's list, largest area first
 //   chains     persistent list-driven wrappers of the three chain kernels: wave per plane on the caller's stream, the lane-per-
 //              plane ring classes on the decoder's side streams (forked and joined with events), thread per chain
 //   samples    unsign_kernel, the inverse DWT with each frame's own size (the level loop on the host runs over `stages`),
 //              finish_kernel; a wave-per-plane chain past its spin bound turns its frame's rc into ICER_FATAL_ERROR
+// The blob stage and the walk are also the first two steps of a re-cut (recut.hpp), which has no copy of either.
 #include "decoder_dplan.hpp"
 #include "wavelet_core.hpp"
 
@@ -25,8 +26,11 @@ constexpr uint32_t kPlanThreads = 1;               // (the mock runs a workgroup
 constexpr uint32_t kPlanThreads = 64;
 #define ICER_BARRIER() __syncthreads()
 #endif
-constexpr uint32_t kPlanChunk = 64;                // candidates summarised per step of plan_kernel's walk
+constexpr uint32_t kPlanChunk = 64;                // candidates summarised per step of walk_frame
 constexpr uint32_t kGroupBytes = 256, kGroupWords = kGroupBytes / 32u, kSuperGroups = 256;
+#ifdef ICER_HOST_MOCK
+constexpr uint32_t kGridCus = 2;                  // (the mock's persistent grids: a few workgroups, each looping)
+#endif
 
 // the head of the workspace: one call's counters (zeroed on the stream)
 struct AsyncHead {
@@ -36,9 +40,38 @@ struct AsyncHead {
     uint32_t place[kRouteKernels][kRouteBuckets];          // next place of a bucket in the lists
 };
 
+// a workspace is carved in 256-byte steps
+struct Carver {
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t p = at; at += (bytes + 255u) & ~(size_t)255u; return p; }
+};
+
+// what the blob stage (enqueue_blob_stage) fills and a frame walk reads: the call's head, the candidates and the buffers that
+// lead to them, and every frame's packet table (tab_off / tab_bits, tab_slots entries a frame)
+struct BlobLayout {
+    size_t head, bitmap, gcount, scount, cands, tab_off, tab_bits;
+    uint32_t groups, supers;
+};
+// `head`: where the caller has put the AsyncHead (the asynchronous decode keeps its frame records between it and the rest)
+BlobLayout blob_layout(Carver &c, size_t head, size_t n, size_t data_bytes, size_t tab_slots)
+{
+    BlobLayout B;
+    B.head = head;
+    B.groups = (uint32_t)((data_bytes + kGroupBytes - 1u) / kGroupBytes);
+    B.supers = (B.groups + kSuperGroups - 1u) / kSuperGroups;
+    B.bitmap = c.take(sizeof(uint32_t) * kGroupWords * (size_t)B.groups);
+    B.gcount = c.take(sizeof(uint32_t) * (size_t)B.groups);
+    B.scount = c.take(sizeof(uint32_t) * (size_t)B.supers);
+    B.cands = c.take(sizeof(DCandRec) * ((data_bytes + 1u) / 2u));     // (two preambles cannot overlap)
+    B.tab_off = c.take(sizeof(uint32_t) * n * tab_slots);
+    B.tab_bits = c.take(sizeof(uint32_t) * n * tab_slots);
+    return B;
+}
+
 struct AsyncLayout {
-    size_t head, frames, ferr, bitmap, gcount, scount, cands, tab_off, tab_bits, chains, lists, tmp, work, pos, total;
-    uint32_t groups, supers, chain_slots, tab_slots;
+    BlobLayout blob;
+    size_t frames, ferr, chains, lists, tmp, work, pos, total;
+    uint32_t chain_slots, tab_slots;
     size_t pos_words;                                       // per frame (uint8 only): odd-length interleave tables
 };
 
@@ -55,29 +88,21 @@ AsyncLayout async_layout(const icerx_decoder *d, int n, size_t data_bytes, size_
     AsyncLayout L;
     const DPlanGeom g = async_geom(d);
     const size_t N = (size_t)n, planes_total = N * (size_t)d->channels * frame_stride;
-    L.groups = (uint32_t)((data_bytes + kGroupBytes - 1u) / kGroupBytes);
-    L.supers = (L.groups + kSuperGroups - 1u) / kSuperGroups;
     L.chain_slots = g.chain_slots();
     L.tab_slots = g.slots();
     // (the lines of a level are at most w + h <= frame_stride / 3 + 3 samples together when the transform runs: both sides >= 3)
     L.pos_words = d->bits == 8 ? 2u * (frame_stride / 3u + 4u) : 0u;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 255u) & ~(size_t)255u; return p; };
-    L.head = take(sizeof(AsyncHead));
-    L.frames = take(sizeof(FrameInfo) * N);
-    L.ferr = take(sizeof(uint32_t) * N);
-    L.bitmap = take(sizeof(uint32_t) * kGroupWords * (size_t)L.groups);
-    L.gcount = take(sizeof(uint32_t) * (size_t)L.groups);
-    L.scount = take(sizeof(uint32_t) * (size_t)L.supers);
-    L.cands = take(sizeof(DCandRec) * ((data_bytes + 1u) / 2u));     // (two preambles cannot overlap)
-    L.tab_off = take(sizeof(uint32_t) * N * L.tab_slots);
-    L.tab_bits = take(sizeof(uint32_t) * N * L.tab_slots);
-    L.chains = take(sizeof(ChainDesc) * N * L.chain_slots);
-    L.lists = take(sizeof(uint32_t) * N * L.chain_slots);
-    L.tmp = take(sizeof(uint16_t) * planes_total);
-    L.work = take(d->bits == 8 || display ? sizeof(uint16_t) * planes_total : 0u);
-    L.pos = take(sizeof(uint32_t) * N * L.pos_words);
-    L.total = at;
+    Carver c;
+    const size_t head = c.take(sizeof(AsyncHead));
+    L.frames = c.take(sizeof(FrameInfo) * N);
+    L.ferr = c.take(sizeof(uint32_t) * N);
+    L.blob = blob_layout(c, head, N, data_bytes, L.tab_slots);
+    L.chains = c.take(sizeof(ChainDesc) * N * L.chain_slots);
+    L.lists = c.take(sizeof(uint32_t) * N * L.chain_slots);
+    L.tmp = c.take(sizeof(uint16_t) * planes_total);
+    L.work = c.take(d->bits == 8 || display ? sizeof(uint16_t) * planes_total : 0u);
+    L.pos = c.take(sizeof(uint32_t) * N * L.pos_words);
+    L.total = c.at;
     return L;
 }
 
@@ -159,11 +184,124 @@ payload_crcs_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const u
     }
 }
 
+// ------------------------------------------------------------------------------------------ blob stage, enqueued
+unsigned grid_blocks(size_t items, size_t per_block, size_t cap)
+{
+    return (unsigned)std::max<size_t>(1, std::min((items + per_block - 1) / per_block, cap));
+}
+uint32_t grid_cus(int n_cus)
+{
+#ifdef ICER_HOST_MOCK
+    return (void)n_cus, kGridCus;
+#else
+    return (uint32_t)n_cus;
+#endif
+}
+
+// the blob stage of a call on `st`: the head zeroed, the packet tables of the n frames emptied, the candidates of the blob
+// with their payload CRCs in offset order (head->n_cands of them)
+int enqueue_blob_stage(const BlobLayout &B, uint8_t *ws, size_t n, size_t tab_slots, const uint8_t *d_data, size_t data_bytes,
+                       const uint32_t *crc_tab, int n_cus, hipStream_t st)
+{
+    int rc = ICER_RESULT_OK;
+    AsyncHead *head = (AsyncHead *)(ws + B.head);
+    DCandRec *recs = (DCandRec *)(ws + B.cands);
+    uint32_t *bitmap = (uint32_t *)(ws + B.bitmap), *gcount = (uint32_t *)(ws + B.gcount), *scount = (uint32_t *)(ws + B.scount);
+    const uint32_t blob_len = (uint32_t)data_bytes;
+    HIP_TRY(hipMemsetAsync(head, 0, sizeof(AsyncHead), st));
+    HIP_TRY(hipMemsetAsync(ws + B.tab_off, 0xFF, sizeof(uint32_t) * n * tab_slots, st));                // (kNoPacket)
+    if (B.groups) {
+        ICER_LAUNCH_ON(st, mark_headers_kernel, (B.groups + 255u) / 256u, 256, 0, d_data, blob_len, crc_tab, bitmap, gcount, B.groups);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, scan_groups_kernel, (B.supers + 255u) / 256u, 256, 0, gcount, B.groups, scount, B.supers);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, scan_supers_kernel, 1, 64, 0, scount, B.supers, head);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, compact_headers_kernel, (B.groups + 255u) / 256u, 256, 0, (const uint32_t *)bitmap, (const uint32_t *)gcount,
+                       (const uint32_t *)scount, B.groups, recs);
+        HIP_TRY(hipGetLastError());
+        ICER_LAUNCH_ON(st, payload_crcs_kernel, grid_blocks((data_bytes + 1u) / 2u, 4, 8u * grid_cus(n_cus)), 256, 0, d_data, blob_len,
+                       crc_tab, recs, head);
+        HIP_TRY(hipGetLastError());
+    }
+done:
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------ per-frame walk
+// What a walk notes besides its DWalk.  other_size and max_level are the re-cut's (recut.hpp): an accepted packet had another
+// image size than the w_in x h_in expected; the largest decomp_level of an accepted packet (0: none).  Accepted: a packet of
+// the frame at or behind the cursor (end != 0 && rel >= cursor), the condition under which dplan_accept moves the cursor.
+struct WalkNotes { uint32_t inside, other_size, max_level; };
+// its dynamic LDS: kPlanChunk DCand, the final DWalk, then for each candidate of the chunk the cursor it met (a word) and its
+// decomp_level (a byte)
+constexpr uint32_t kWalkCursorAt = kPlanChunk * sizeof(DCand) + sizeof(DWalk), kWalkLevelsAt = kWalkCursorAt + kPlanChunk * sizeof(uint32_t);
+constexpr uint32_t kWalkLds = kWalkLevelsAt + kPlanChunk;
+
+// The decoder's cursor walk of frame [off, off + len) into its packet table `to` / `tb`, called by the WHOLE workgroup, of any
+// size.  Per kPlanChunk candidates: the threads summarise them into LDS; thread 0 runs the cursor rule over the summaries,
+// the one serial step, which takes nothing else along but a store of the cursor each candidate met; the threads then look at
+// their own candidates for the notes.  Returns the final DWalk (in: w_in, h_in) and fills *notes, the same in every
+// thread.  A frame outside the blob (notes->inside = 0) is not walked.  Which barriers a workgroup meets depends on the
+// frame alone, never on the thread, so all threads reach every one of them.
+ICER_DEV DWalk walk_frame(uint8_t *lds, const uint8_t *blob, uint32_t blob_len, uint64_t off, uint64_t len, const DCandRec *recs,
+                          const AsyncHead *head, const DPlanGeom &geom, uint64_t w_in, uint64_t h_in, uint32_t *to, uint32_t *tb,
+                          WalkNotes *notes)
+{
+    DCand *chunk = reinterpret_cast<DCand *>(lds);
+    DWalk *shared_walk = reinterpret_cast<DWalk *>(lds + kPlanChunk * sizeof(DCand));
+    uint32_t *cursor_at = reinterpret_cast<uint32_t *>(lds + kWalkCursorAt);
+    uint8_t *levels = lds + kWalkLevelsAt;
+    const uint32_t tid = threadIdx.x;
+    const bool inside = off <= blob_len && len <= blob_len - off;
+    DWalk s;
+    dwalk_init(&s, w_in, h_in);
+    uint32_t other = 0, top = 0;                               // over the accepted candidates that this thread summarised
+    if (inside) {
+        const uint32_t nc = head->n_cands, first = dlower_bound(recs, nc, (uint32_t)off), last = dlower_bound(recs, nc, (uint32_t)(off + len));
+        for (uint32_t at = first; at < last; at += kPlanChunk) {
+            const uint32_t m = last - at < kPlanChunk ? last - at : kPlanChunk;
+            for (uint32_t t = tid; t < m; t += blockDim.x) {
+                chunk[t] = dplan_summary(geom, blob, (uint32_t)off, (uint32_t)len, recs[at + t]);
+                levels[t] = chunk[t].end != 0 ? blob[recs[at + t].off + 4u] : (uint8_t)0;
+            }
+            ICER_BARRIER();
+            if (tid == 0)
+                for (uint32_t t = 0; t < m; t++) {
+                    cursor_at[t] = s.cursor;
+                    dplan_accept(&s, chunk[t], to, tb);
+                }
+            ICER_BARRIER();
+            // (candidate t is summarised and looked at by the same thread, and its cursor is written again behind the next barrier)
+            for (uint32_t t = tid; t < m; t += blockDim.x)
+                if (chunk[t].end != 0 && chunk[t].rel >= cursor_at[t]) {
+                    if (chunk[t].w != w_in || chunk[t].h != h_in) other = 1;
+                    if (levels[t] > top) top = levels[t];
+                }
+        }
+    }
+    // every thread's part through the chunk's LDS, free now: a word per thread that can have summarised a candidate
+    static_assert(sizeof(uint32_t) <= sizeof(DCand), "a word per thread fits the chunk");
+    uint32_t *part = reinterpret_cast<uint32_t *>(chunk);
+    const uint32_t parts = blockDim.x < kPlanChunk ? blockDim.x : kPlanChunk;
+    ICER_BARRIER();
+    if (tid < parts) part[tid] = top | other << 31;
+    if (tid == 0) *shared_walk = s;
+    ICER_BARRIER();
+    notes->inside = inside ? 1u : 0u; notes->other_size = 0; notes->max_level = 0;
+    for (uint32_t i = 0; i < parts; i++) {
+        const uint32_t v = part[i], lv = v & 0x7FFFFFFFu;
+        notes->other_size |= v >> 31;
+        if (lv > notes->max_level) notes->max_level = lv;
+    }
+    return *shared_walk;
+}
+
 // ------------------------------------------------------------------------------------------ per-frame plan
 // one workgroup per frame.  Frame k = blob bytes [off, off + len), off = offsets[k] or k * stream_stride; a frame outside
-// the blob gets ICER_INVALID_INPUT and no chains.  The walk: the threads summarise kPlanChunk candidates into LDS, thread 0
-// runs the cursor rule over them; then every thread builds chain slots.  Writes rcs / ws / hs (ws / hs: in = the values kept
-// when the frame holds no valid packet), the FrameInfo and the frame's chain slots (kNoChain where plan_decode has none).
+// the blob gets ICER_INVALID_INPUT and no chains.  After the walk every thread builds chain slots.  Writes rcs / ws / hs
+// (ws / hs: in = the values kept when the frame holds no valid packet), the FrameInfo and the frame's chain slots (kNoChain
+// where plan_decode has none).
 __global__ void __launch_bounds__(64)
 plan_frames_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uint64_t *__restrict__ offsets, uint64_t stream_stride,
                    const uint64_t *__restrict__ lens, const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head,
@@ -171,15 +309,14 @@ plan_frames_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const ui
                    ChainDesc *__restrict__ chains, FrameInfo *__restrict__ frames, int32_t *__restrict__ rcs,
                    uint64_t *__restrict__ ws, uint64_t *__restrict__ hs)
 {
-    ICER_DYNAMIC_LDS(uint8_t, lds);                            // kPlanChunk DCand, then the walk's result
-    DCand *chunk = reinterpret_cast<DCand *>(lds);
-    DWalk *shared_walk = reinterpret_cast<DWalk *>(lds + kPlanChunk * sizeof(DCand));
+    ICER_DYNAMIC_LDS(uint8_t, lds);                            // kWalkLds
     const uint32_t k = blockIdx.x, tid = threadIdx.x;
     const uint64_t off = offsets ? offsets[k] : (uint64_t)k * stream_stride, len = lens[k];
-    const bool inside = off <= blob_len && len <= blob_len - off;
     uint32_t *to = tab_off + (size_t)k * geom.slots(), *tb = tab_bits + (size_t)k * geom.slots();
     ChainDesc *mine = chains + (size_t)k * geom.chain_slots();
-    if (!inside) {
+    WalkNotes notes;
+    const DWalk s = walk_frame(lds, blob, blob_len, off, len, recs, head, geom, ws[k], hs[k], to, tb, &notes);
+    if (!notes.inside) {
         if (tid == 0) {
             const FrameInfo f = {};
             frames[k] = f;
@@ -188,19 +325,6 @@ plan_frames_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const ui
         for (uint32_t j = tid; j < geom.chain_slots(); j += blockDim.x) mine[j].frame = kNoChain;
         return;
     }
-    const uint32_t n = head->n_cands, first = dlower_bound(recs, n, (uint32_t)off), last = dlower_bound(recs, n, (uint32_t)(off + len));
-    DWalk s;
-    dwalk_init(&s, ws[k], hs[k]);
-    for (uint32_t at = first; at < last; at += kPlanChunk) {
-        const uint32_t m = last - at < kPlanChunk ? last - at : kPlanChunk;
-        for (uint32_t t = tid; t < m; t += blockDim.x) chunk[t] = dplan_summary(geom, blob, (uint32_t)off, (uint32_t)len, recs[at + t]);
-        ICER_BARRIER();
-        if (tid == 0) for (uint32_t t = 0; t < m; t++) dplan_accept(&s, chunk[t], to, tb);
-        ICER_BARRIER();
-    }
-    if (tid == 0) *shared_walk = s;
-    ICER_BARRIER();
-    s = *shared_walk;
     const DPlanResult res = dplan_finish(geom, s, bufsize);
     if (tid == 0) {
         FrameInfo f;
@@ -419,10 +543,6 @@ fatal_frames_kernel(const uint32_t *__restrict__ ferr, int32_t *__restrict__ rcs
 }
 
 // ------------------------------------------------------------------------------------------ host side
-#ifdef ICER_HOST_MOCK
-constexpr uint32_t kGridCus = 2;                  // (the mock's persistent grids: a few workgroups, each looping)
-#endif
-
 int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
                  const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs,
                  void *workspace, size_t workspace_bytes, hipStream_t st, uint8_t *d_display = nullptr)
@@ -441,10 +561,10 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     const int nplanes = bits == 8 ? kPlanes8 : kPlanes, sign_bit = bits == 8 ? 7 : 15;
     const DPlanGeom geom = async_geom(d);
     uint8_t *ws = (uint8_t *)workspace;
-    AsyncHead *head = (AsyncHead *)(ws + L.head);
+    AsyncHead *head = (AsyncHead *)(ws + L.blob.head);
     FrameInfo *frames = (FrameInfo *)(ws + L.frames);
     uint32_t *ferr = (uint32_t *)(ws + L.ferr);
-    DCandRec *recs = (DCandRec *)(ws + L.cands);
+    DCandRec *recs = (DCandRec *)(ws + L.blob.cands);
     ChainDesc *chains = (ChainDesc *)(ws + L.chains);
     uint32_t *lists = (uint32_t *)(ws + L.lists);
     uint32_t *pos = (uint32_t *)(ws + L.pos);
@@ -453,12 +573,8 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     const uint32_t blob_len = (uint32_t)data_bytes, slots = (uint32_t)n * L.chain_slots;
     const size_t planes_total = (size_t)n * channels * frame_stride;
     uint16_t *planes = bits == 16 && !d_display ? (uint16_t *)d_out : (uint16_t *)(ws + L.work);
-#ifdef ICER_HOST_MOCK
-    const uint32_t cus = kGridCus;
-#else
-    const uint32_t cus = (uint32_t)d->n_cus;
-#endif
-    auto grid = [](size_t items, size_t per_block, size_t cap) { return (unsigned)std::max<size_t>(1, std::min((items + per_block - 1) / per_block, cap)); };
+    const uint32_t cus = grid_cus(d->n_cus);
+    const auto grid = grid_blocks;
 
     // which kernel decodes a chain: decode_batch's rule, decided on the device (ICER_DEC_WAVE read per call, as there)
     DRouteRule rule;
@@ -506,29 +622,13 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     }
 
     // 1. candidates over the blob
-    HIP_TRY(hipMemsetAsync(head, 0, sizeof(AsyncHead), st));
     HIP_TRY(hipMemsetAsync(ferr, 0, sizeof(uint32_t) * n, st));
-    HIP_TRY(hipMemsetAsync(ws + L.tab_off, 0xFF, sizeof(uint32_t) * (size_t)n * L.tab_slots, st));      // (kNoPacket)
-    if (L.groups) {
-        ICER_LAUNCH_ON(st, mark_headers_kernel, (L.groups + 255u) / 256u, 256, 0, d_data, blob_len, crc_tab, (uint32_t *)(ws + L.bitmap),
-                       (uint32_t *)(ws + L.gcount), L.groups);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, scan_groups_kernel, (L.supers + 255u) / 256u, 256, 0, (uint32_t *)(ws + L.gcount), L.groups,
-                       (uint32_t *)(ws + L.scount), L.supers);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, scan_supers_kernel, 1, 64, 0, (uint32_t *)(ws + L.scount), L.supers, head);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, compact_headers_kernel, (L.groups + 255u) / 256u, 256, 0, (const uint32_t *)(ws + L.bitmap),
-                       (const uint32_t *)(ws + L.gcount), (const uint32_t *)(ws + L.scount), L.groups, recs);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, payload_crcs_kernel, grid((data_bytes + 1u) / 2u, 4, 8u * cus), 256, 0, d_data, blob_len, crc_tab, recs, head);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = enqueue_blob_stage(L.blob, ws, (size_t)n, L.tab_slots, d_data, data_bytes, crc_tab, d->n_cus, st)) != ICER_RESULT_OK) goto done;
 
     // 2. plans
-    ICER_LAUNCH_ON(st, plan_frames_kernel, (unsigned)n, kPlanThreads, kPlanChunk * sizeof(DCand) + sizeof(DWalk), d_data, blob_len,
-                   d_offsets, (uint64_t)stream_stride, d_lens, recs, head, geom, (uint64_t)frame_stride, (uint32_t *)(ws + L.tab_off),
-                   (uint32_t *)(ws + L.tab_bits), chains, frames, d_rcs, d_ws, d_hs);
+    ICER_LAUNCH_ON(st, plan_frames_kernel, (unsigned)n, kPlanThreads, kWalkLds, d_data, blob_len, d_offsets, (uint64_t)stream_stride,
+                   d_lens, recs, head, geom, (uint64_t)frame_stride, (uint32_t *)(ws + L.blob.tab_off), (uint32_t *)(ws + L.blob.tab_bits),
+                   chains, frames, d_rcs, d_ws, d_hs);
     HIP_TRY(hipGetLastError());
     if (planes_total == 0) goto done;
 

@@ -1,20 +1,16 @@
-// recut.hpp -- icerx_recut_device_async (include/icer_hip_dec.h): stored streams ("masters") re-cut to smaller byte quotas
-// on the device, without the pixels and without re-coding.  Included by decoder.hip after decoder_async.hpp, whose blob
-// pass it reuses as it is.
+// recut.hpp -- icerx_recut_device_async and icerx_recut_device_cuts_async (include/icer_hip_dec.h): stored streams ("masters")
+// re-cut on the device, without the pixels and without re-coding.  A cut is (reduce r, quota): the master's derived stream at
+// 1/2^r size, cut at that byte quota; the byte-quota call is the call whose every reduce is 0, in a smaller workspace.
+// Included by decoder.hip after decoder_async.hpp, whose blob stage and frame walk are the first two steps here as well.
 //
-//   blob       the candidate kernels of the asynchronous decode over the whole blob (mark_headers_kernel ... payload_crcs_kernel)
-//   frames     recut_plan_kernel, one workgroup per frame: the decoder's cursor walk into the frame's packet table, the
-//              units' bit counts through the recutter's unit -> table slot map (recut_core.hpp), then one wavefront per
-//              quota: the quota walk of the rate ladder (scan_ladder_wave) -> final offsets, size, return code
-//   packets    recut_gather_kernel, one workgroup per (unit, frame): the packet copied verbatim to every quota's stream
-//              that keeps it (copy_unit_recut)
+//   blob       enqueue_blob_stage: the candidate kernels of the asynchronous decode over the whole blob
+//   frames     recut_plan_kernel, one workgroup per frame: the decoder's cursor walk (walk_frame) into the frame's packet
+//              table, once; the units' bit counts of every geometry in use through that geometry's unit -> table slot map
+//              (recut_core.hpp); then one wavefront per cut: the quota walk of the rate ladder (scan_ladder_wave) with the
+//              tables of the geometry at 1/2^r size -> final offsets, size, return code
+//   packets    recut_gather_kernel, one workgroup per (unit of the master, frame): the payload copied as it is to every cut
+//              that keeps the packet (copy_unit_recut), the 28 header bytes written per cut (recut_cut_header; r = 0: a copy)
 // Everything is enqueued on the caller's stream; the caller owns the workspace (recut_layout).
-//
-// icerx_recut_device_cuts_async cuts by resolution as well: a cut is (reduce r, quota), the re-cut of the master's derived
-// stream at 1/2^r size.  Its frames step (recut_cuts_plan_kernel) makes the packet table once and runs every cut's walk with
-// the tables of the geometry at 1/2^r size; its packets step (recut_cuts_gather_kernel) is still one workgroup per packet of
-// the master: the payload is copied as it is, the 28 header bytes are written per cut (recut_cut_header).  A call whose
-// reduces are all 0 takes the kernels above.
 #include "recut_core.hpp"
 
 #ifdef ICER_WAVE_EMU
@@ -25,19 +21,18 @@ struct icerx_recutter {
     int device = 0;
     uint64_t w = 0, h = 0;
     DPlanGeom geom{};
-    uint32_t n_units = 0;
     int n_cus = 256;
-    // device tables, uploaded once: CRC-32 table, table slot of every unit and the D7 final order (Plan::units order), the
-    // unit table itself (scan_ladder_wave reads cap_is_bound of the unit at the cut: 0 here)
-    void *crc = nullptr, *unit_slot = nullptr, *final_order = nullptr, *units = nullptr;
-    // icerx_recutter_create_reduced: the same three tables for the geometry at 1/2^r size, r = 1 .. max_reduce, built by the
-    // planner on that geometry, and full_to_cut[u]: the unit there that unit u of the full geometry stands for (kNoPacket: none)
+    void *crc = nullptr;                              // CRC-32 table
+    // device tables of the geometry at 1/2^r size, r = 0 .. max_reduce (0 unless icerx_recutter_create_reduced), uploaded once
+    // and built by the planner on that geometry: table slot of every unit and the D7 final order (Plan::units order), the unit
+    // table itself (scan_ladder_wave reads cap_is_bound of the unit at the cut: 0 here), and for r > 0 full_to_cut[u]: the unit
+    // there that unit u of the full geometry stands for (kNoPacket: none)
     int max_reduce = 0;
     struct Reduced {
         uint32_t n_units = 0;
         void *unit_slot = nullptr, *final_order = nullptr, *units = nullptr, *full_to_cut = nullptr;
     } red[kRecutMaxReduce + 1];
-    uint32_t units_total = 0;                         // n_units + red[1 .. max_reduce].n_units
+    uint32_t units_total = 0;                         // red[0 .. max_reduce].n_units together
 };
 
 extern "C" void icerx_recutter_destroy(icerx_recutter *r);
@@ -52,8 +47,9 @@ constexpr uint32_t kRecutPlanThreads = 256, kRecutGatherThreads = 256;
 constexpr int kRecutMaxFrames = 65535;            // (frames are the y dimension of the gather's grid)
 
 struct RecutLayout {
-    size_t head, bitmap, gcount, scount, cands, tab_off, tab_bits, bits, foff, by_unit, total;
-    uint32_t groups, supers;
+    BlobLayout blob;
+    size_t bits, foff, by_unit, total;
+    uint32_t bits_stride;                             // bit counts a frame
 };
 
 // the tables of every geometry and the cuts of a call, passed by value with the launches
@@ -67,152 +63,47 @@ struct RecutCuts {
     uint8_t reduce[kMaxLadder];
 };
 
+// The byte-quota call: a frame's bit counts for the full geometry, each quota's final offsets (foff, rows of n_units entries).
 // cuts: the workspace of icerx_recut_device_cuts_async -- bit counts for every geometry, and each cut's final offsets twice,
 // in the order of its own geometry's units (by_unit) and in the order of the master's (foff); rows of n_units entries both
-RecutLayout recut_layout(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas, bool cuts = false)
+RecutLayout recut_layout(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts, bool cuts)
 {
     RecutLayout L;
-    const size_t N = (size_t)n, slots = r->geom.slots();
-    L.groups = (uint32_t)((data_bytes + kGroupBytes - 1u) / kGroupBytes);
-    L.supers = (L.groups + kSuperGroups - 1u) / kSuperGroups;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t p = at; at += (bytes + 255u) & ~(size_t)255u; return p; };
-    L.head = take(sizeof(AsyncHead));
-    L.bitmap = take(sizeof(uint32_t) * kGroupWords * (size_t)L.groups);
-    L.gcount = take(sizeof(uint32_t) * (size_t)L.groups);
-    L.scount = take(sizeof(uint32_t) * (size_t)L.supers);
-    L.cands = take(sizeof(DCandRec) * ((data_bytes + 1u) / 2u));     // (two preambles cannot overlap)
-    L.tab_off = take(sizeof(uint32_t) * N * slots);
-    L.tab_bits = take(sizeof(uint32_t) * N * slots);
-    L.bits = take(sizeof(uint32_t) * N * (cuts ? r->units_total : r->n_units));
-    L.foff = take(sizeof(uint64_t) * N * r->n_units * (size_t)n_quotas);
-    L.by_unit = cuts ? take(sizeof(uint64_t) * N * r->n_units * (size_t)n_quotas) : at;
-    L.total = at;
+    const size_t N = (size_t)n, n_full = r->red[0].n_units;
+    Carver c;
+    const size_t head = c.take(sizeof(AsyncHead));
+    L.blob = blob_layout(c, head, N, data_bytes, r->geom.slots());
+    L.bits_stride = cuts ? r->units_total : r->red[0].n_units;
+    L.bits = c.take(sizeof(uint32_t) * N * L.bits_stride);
+    L.foff = c.take(sizeof(uint64_t) * N * n_full * (size_t)n_cuts);
+    L.by_unit = cuts ? c.take(sizeof(uint64_t) * N * n_full * (size_t)n_cuts) : c.at;
+    L.total = c.at;
     return L;
 }
 
-// LDS of the walks: kPlanChunk DCand, the walk's result, two flags; for the cuts, kPlanChunk decomp_level bytes behind them
-constexpr uint32_t kRecutWalkLds = kPlanChunk * sizeof(DCand) + sizeof(DWalk) + 16u, kRecutWalkLevelsLds = kRecutWalkLds + kPlanChunk;
-
-// recut_plan_kernel's walk for the cuts (a body of its own, so that the byte-quota kernel stays as it was measured): the
-// decoder's cursor walk of the frame [off, off + len) into its packet table `to` / `tb`, by the whole workgroup -- the
-// threads summarise kPlanChunk candidates into LDS, thread 0 runs the cursor rule over them and notes a valid packet of
-// another image size.  Returns the frame's status (recut_frame_status), the same in every thread; *max_level is the
-// largest decomp_level of a packet the walk accepted (0: none).
-ICER_DEV int recut_walk_frame(uint8_t *lds, const uint8_t *blob, uint32_t blob_len, uint64_t off, uint64_t len, const DCandRec *recs,
-                              const AsyncHead *head, const DPlanGeom &geom, uint64_t image_w, uint64_t image_h, uint32_t *to, uint32_t *tb,
-                              uint32_t *max_level)
-{
-    DCand *chunk = reinterpret_cast<DCand *>(lds);
-    DWalk *shared_walk = reinterpret_cast<DWalk *>(lds + kPlanChunk * sizeof(DCand));
-    uint32_t *shared_other = reinterpret_cast<uint32_t *>(lds + kPlanChunk * sizeof(DCand) + sizeof(DWalk));
-    uint8_t *levels = lds + kRecutWalkLds;
-    const uint32_t tid = threadIdx.x;
-    const bool inside = off <= blob_len && len <= blob_len - off;
-    DWalk s;
-    dwalk_init(&s, image_w, image_h);
-    uint32_t other = 0, top = 0;
-    if (inside) {
-        const uint32_t nc = head->n_cands, first = dlower_bound(recs, nc, (uint32_t)off), last = dlower_bound(recs, nc, (uint32_t)(off + len));
-        for (uint32_t at = first; at < last; at += kPlanChunk) {
-            const uint32_t m = last - at < kPlanChunk ? last - at : kPlanChunk;
-            for (uint32_t t = tid; t < m; t += blockDim.x) {
-                chunk[t] = dplan_summary(geom, blob, (uint32_t)off, (uint32_t)len, recs[at + t]);
-                levels[t] = chunk[t].end != 0 ? blob[recs[at + t].off + 4u] : (uint8_t)0;
-            }
-            ICER_BARRIER();
-            if (tid == 0)
-                for (uint32_t t = 0; t < m; t++) {
-                    if (chunk[t].end != 0 && chunk[t].rel >= s.cursor) {
-                        if (chunk[t].w != image_w || chunk[t].h != image_h) other = 1;
-                        if (levels[t] > top) top = levels[t];
-                    }
-                    dplan_accept(&s, chunk[t], to, tb);
-                }
-            ICER_BARRIER();
-        }
-    }
-    if (tid == 0) { *shared_walk = s; shared_other[0] = other; shared_other[1] = top; }
-    ICER_BARRIER();
-    *max_level = shared_other[1];
-    return recut_frame_status(inside, shared_walk->cursor, shared_other[0] != 0u);
-}
-
-// one workgroup per frame (frame k addressed as in plan_frames_kernel).  The walk: the threads summarise kPlanChunk
-// candidates into LDS, thread 0 runs the cursor rule over them and notes a valid packet of another image size; then every
-// thread reads unit bit counts out of the packet table, and wavefront v takes the quotas v, v + waves, ...: row q * n + k of
-// sizes / rcs, final offsets foff[(q * n + k) * n_units ..].
+// one workgroup per frame (frame k addressed as in plan_frames_kernel): the packet table once, then the bit counts of every
+// geometry in use (bit r of `used`) through that geometry's slot map (bits_stride counts a frame), and wavefront v takes the
+// cuts v, v + waves, ...: the walk with the tables of the cut's geometry leaves the final offsets in the order of that
+// geometry's units (by_unit; reduce 0: foff at once), and the workgroup turns them into the order of the master's units,
+// which the gather goes by.  Row c * n + k of sizes / rcs and of foff / by_unit (n_units[0] entries a row).  A call whose
+// every reduce is 0 touches neither by_unit nor a bit count past the full geometry's (bits_at[0] = 0).
 __global__ void __launch_bounds__(256)
 recut_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uint64_t *__restrict__ offsets, uint64_t stream_stride,
                   const uint64_t *__restrict__ lens, const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head,
-                  DPlanGeom geom, uint64_t image_w, uint64_t image_h, const uint32_t *__restrict__ unit_slot,
-                  const uint32_t *__restrict__ final_order, const UnitDesc *__restrict__ units, uint32_t n_units,
-                  LadderQuotas quotas, uint32_t n_q, uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits,
-                  uint32_t *__restrict__ unit_bits, uint64_t *__restrict__ foff, unsigned long long *__restrict__ sizes,
-                  int32_t *__restrict__ rcs)
+                  DPlanGeom geom, uint64_t image_w, uint64_t image_h, RecutCutTables tabs, uint32_t bits_stride, RecutCuts cuts,
+                  uint32_t n_c, uint32_t used, uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits,
+                  uint32_t *__restrict__ unit_bits, uint64_t *__restrict__ foff, uint64_t *__restrict__ by_unit,
+                  unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs)
 {
-    ICER_DYNAMIC_LDS(uint8_t, lds);                            // kPlanChunk DCand, then the walk's result
-    DCand *chunk = reinterpret_cast<DCand *>(lds);
-    DWalk *shared_walk = reinterpret_cast<DWalk *>(lds + kPlanChunk * sizeof(DCand));
-    uint32_t *shared_other = reinterpret_cast<uint32_t *>(lds + kPlanChunk * sizeof(DCand) + sizeof(DWalk));
-    const uint32_t k = blockIdx.x, n = gridDim.x, tid = threadIdx.x;
-    const uint64_t off = offsets ? offsets[k] : (uint64_t)k * stream_stride, len = lens[k];
-    const bool inside = off <= blob_len && len <= blob_len - off;
-    uint32_t *to = tab_off + (size_t)k * geom.slots(), *tb = tab_bits + (size_t)k * geom.slots();
-    uint32_t *bits = unit_bits + (size_t)k * n_units;
-    DWalk s;
-    dwalk_init(&s, image_w, image_h);
-    uint32_t other = 0;
-    if (inside) {
-        const uint32_t nc = head->n_cands, first = dlower_bound(recs, nc, (uint32_t)off), last = dlower_bound(recs, nc, (uint32_t)(off + len));
-        for (uint32_t at = first; at < last; at += kPlanChunk) {
-            const uint32_t m = last - at < kPlanChunk ? last - at : kPlanChunk;
-            for (uint32_t t = tid; t < m; t += blockDim.x) chunk[t] = dplan_summary(geom, blob, (uint32_t)off, (uint32_t)len, recs[at + t]);
-            ICER_BARRIER();
-            if (tid == 0)
-                for (uint32_t t = 0; t < m; t++) {
-                    if (chunk[t].end != 0 && chunk[t].rel >= s.cursor && (chunk[t].w != image_w || chunk[t].h != image_h)) other = 1;
-                    dplan_accept(&s, chunk[t], to, tb);
-                }
-            ICER_BARRIER();
-        }
-    }
-    if (tid == 0) { *shared_walk = s; *shared_other = other; }
-    ICER_BARRIER();
-    const int status = recut_frame_status(inside, shared_walk->cursor, *shared_other != 0u);
-    if (status == kOk) recut_unit_bits(to, tb, unit_slot, n_units, bits, tid, blockDim.x);
-    ICER_BARRIER();
-#ifdef ICER_HOST_MOCK
-    const uint32_t wave = 0, waves = 1;
-#else
-    const uint32_t wave = tid >> 6, waves = blockDim.x >> 6;
-#endif
-    for (uint32_t q = wave; q < n_q; q += waves) {
-        const size_t row = (size_t)q * n + k;
-        recut_scan_wave(status, bits, final_order, n_units, quotas.q[q], units, foff + row * n_units, sizes + row, rcs + row);
-    }
-}
-
-// recut_plan_kernel for cuts: the packet table once per frame, then the bit counts of every geometry in use (bit r of
-// `used`) through that geometry's slot map, and wavefront v takes the cuts v, v + waves, ...: the walk with the tables of
-// the cut's geometry leaves the final offsets in the order of that geometry's units (by_unit; reduce 0: foff at once), and
-// the workgroup turns them into the order of the master's units, which the gather goes by.  Row c * n + k of sizes / rcs
-// and of foff / by_unit (n_units[0] entries a row).
-__global__ void __launch_bounds__(256)
-recut_cuts_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uint64_t *__restrict__ offsets, uint64_t stream_stride,
-                       const uint64_t *__restrict__ lens, const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head,
-                       DPlanGeom geom, uint64_t image_w, uint64_t image_h, RecutCutTables tabs, uint32_t units_total, RecutCuts cuts,
-                       uint32_t n_c, uint32_t used, uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits,
-                       uint32_t *__restrict__ unit_bits, uint64_t *__restrict__ foff, uint64_t *__restrict__ by_unit,
-                       unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs)
-{
-    ICER_DYNAMIC_LDS(uint8_t, lds);
+    ICER_DYNAMIC_LDS(uint8_t, lds);                            // kWalkLds
     const uint32_t k = blockIdx.x, n = gridDim.x, tid = threadIdx.x, n_full = tabs.n_units[0];
     const uint64_t off = offsets ? offsets[k] : (uint64_t)k * stream_stride, len = lens[k];
     uint32_t *to = tab_off + (size_t)k * geom.slots(), *tb = tab_bits + (size_t)k * geom.slots();
-    uint32_t *bits = unit_bits + (size_t)k * units_total;
-    uint32_t max_level = 0;
-    const int status = recut_walk_frame(lds, blob, blob_len, off, len, recs, head, geom, image_w, image_h, to, tb, &max_level);
+    uint32_t *bits = unit_bits + (size_t)k * bits_stride;
+    WalkNotes notes;
+    const DWalk s = walk_frame(lds, blob, blob_len, off, len, recs, head, geom, image_w, image_h, to, tb, &notes);
+    const int status = recut_frame_status(notes.inside != 0u, s.cursor, notes.other_size != 0u);
+    const uint32_t max_level = notes.max_level;
     for (uint32_t r = 0; r <= (uint32_t)kRecutMaxReduce; r++)
         if (((used >> r) & 1u) && recut_cut_status(status, max_level, r) == kOk)
             recut_unit_bits(to, tb, tabs.unit_slot[r], tabs.n_units[r], bits + tabs.bits_at[r], tid, blockDim.x);
@@ -236,39 +127,19 @@ recut_cuts_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, cons
     }
 }
 
-// one workgroup per (unit, frame): the unit's packet, wherever it lies in the master, to every quota's stream that keeps it
+// one workgroup per (unit of the master, frame): the unit's packet, wherever it lies in the master, to every cut's stream that
+// keeps it.  The payload goes as it is, from byte 28 on; the header of cut c is written by thread c as it stands in the
+// derived stream at the cut's reduce (recut_cut_header), so no two threads write the same byte.
 __global__ void __launch_bounds__(256)
 recut_gather_kernel(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets, uint64_t stream_stride, DPlanGeom geom,
                     const uint32_t *__restrict__ unit_slot, uint32_t n_units, const uint32_t *__restrict__ tab_off,
-                    const uint32_t *__restrict__ unit_bits, const uint64_t *__restrict__ foff, uint32_t n_q, uint8_t *__restrict__ out,
-                    size_t out_stride)
-{
-    const uint32_t ui = blockIdx.x, frame = blockIdx.y, n = gridDim.y;
-    const size_t off_pitch = (size_t)n * n_units;
-    const uint64_t *offs = foff + (size_t)frame * n_units + ui;
-    // (a frame with a status, a unit without a packet, a unit behind every cut: nothing to copy, and nothing of it is looked at)
-    bool any = false;
-    for (uint32_t q = 0; q < n_q; q++) any |= offs[(size_t)q * off_pitch] != ~0ull;
-    if (!any) return;
-    const uint64_t off = offsets ? offsets[frame] : (uint64_t)frame * stream_stride;
-    const uint32_t len = (uint32_t)kHeaderBytes + ((unit_bits[(size_t)frame * n_units + ui] + 7u) >> 3);
-    // (the walk accepted this packet: header and payload lie inside the frame, and the frame inside the blob)
-    copy_unit_recut(blob + off + tab_off[(size_t)frame * geom.slots() + unit_slot[ui]], len, offs, off_pitch, n_q,
-                    out + (size_t)frame * out_stride, (size_t)n * out_stride, threadIdx.x, blockDim.x);
-}
-
-// recut_gather_kernel for cuts, still one workgroup per (unit of the master, frame): the payload goes as it is to every cut
-// that keeps the packet, from byte 28 on; the header of cut c is written by thread c as it stands in the derived stream
-// at the cut's reduce (recut_cut_header), so no two threads write the same byte.
-__global__ void __launch_bounds__(256)
-recut_cuts_gather_kernel(const uint8_t *__restrict__ blob, const uint64_t *__restrict__ offsets, uint64_t stream_stride, DPlanGeom geom,
-                         const uint32_t *__restrict__ unit_slot, uint32_t n_units, const uint32_t *__restrict__ tab_off,
-                         const uint32_t *__restrict__ tab_bits, const uint64_t *__restrict__ foff, RecutCuts cuts, uint32_t n_c,
-                         const uint32_t *__restrict__ crc_tab, uint8_t *__restrict__ out, size_t out_stride)
+                    const uint32_t *__restrict__ tab_bits, const uint64_t *__restrict__ foff, RecutCuts cuts, uint32_t n_c,
+                    const uint32_t *__restrict__ crc_tab, uint8_t *__restrict__ out, size_t out_stride)
 {
     const uint32_t ui = blockIdx.x, frame = blockIdx.y, n = gridDim.y;
     const size_t off_pitch = (size_t)n * n_units, q_pitch = (size_t)n * out_stride;
     const uint64_t *offs = foff + (size_t)frame * n_units + ui;
+    // (a frame with a status, a unit without a packet, a unit behind every cut: nothing to copy, and nothing of it is looked at)
     bool any = false;
     for (uint32_t c = 0; c < n_c; c++) any |= offs[(size_t)c * off_pitch] != ~0ull;
     if (!any) return;
@@ -290,107 +161,36 @@ hipError_t recut_upload(void **p, const void *src, size_t bytes)
     return e != hipSuccess ? e : hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice);
 }
 
-// step 1 of both calls: the candidates over the blob (decode_async's step 1), and every frame's packet table emptied
-int recut_blob_pass(const icerx_recutter *r, const RecutLayout &L, uint8_t *ws, int n, const uint8_t *d_data, size_t data_bytes, hipStream_t st)
-{
-    int rc = ICER_RESULT_OK;
-    AsyncHead *head = (AsyncHead *)(ws + L.head);
-    DCandRec *recs = (DCandRec *)(ws + L.cands);
-    const uint32_t *crc_tab = (const uint32_t *)r->crc;
-    const uint32_t blob_len = (uint32_t)data_bytes;
-#ifdef ICER_HOST_MOCK
-    const uint32_t cus = kGridCus;
-#else
-    const uint32_t cus = (uint32_t)r->n_cus;
-#endif
-    auto grid = [](size_t items, size_t per_block, size_t cap) { return (unsigned)std::max<size_t>(1, std::min((items + per_block - 1) / per_block, cap)); };
-    HIP_TRY(hipMemsetAsync(head, 0, sizeof(AsyncHead), st));
-    HIP_TRY(hipMemsetAsync(ws + L.tab_off, 0xFF, sizeof(uint32_t) * (size_t)n * r->geom.slots(), st));          // (kNoPacket)
-    if (L.groups) {
-        ICER_LAUNCH_ON(st, mark_headers_kernel, (L.groups + 255u) / 256u, 256, 0, d_data, blob_len, crc_tab, (uint32_t *)(ws + L.bitmap),
-                       (uint32_t *)(ws + L.gcount), L.groups);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, scan_groups_kernel, (L.supers + 255u) / 256u, 256, 0, (uint32_t *)(ws + L.gcount), L.groups,
-                       (uint32_t *)(ws + L.scount), L.supers);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, scan_supers_kernel, 1, 64, 0, (uint32_t *)(ws + L.scount), L.supers, head);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, compact_headers_kernel, (L.groups + 255u) / 256u, 256, 0, (const uint32_t *)(ws + L.bitmap),
-                       (const uint32_t *)(ws + L.gcount), (const uint32_t *)(ws + L.scount), L.groups, recs);
-        HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(st, payload_crcs_kernel, grid((data_bytes + 1u) / 2u, 4, 8u * cus), 256, 0, d_data, blob_len, crc_tab, recs, head);
-        HIP_TRY(hipGetLastError());
-    }
-done:
-    return rc;
-}
-
+// Both calls.  by_resolution = false: the byte-quota call -- `reduces` is not looked at, every reduce is 0, and the workspace
+// is its own smaller one (recut_layout), outside of which the kernels then touch nothing.  Every check comes before the
+// first thing enqueued: a refused call writes nothing.
 int recut_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
-                const uint64_t *d_lens, const size_t *quotas, int n_quotas, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes,
-                int32_t *d_rcs, void *workspace, size_t workspace_bytes, hipStream_t st)
-{
-    g_error.clear();
-    if (!r || n < 1 || n > kRecutMaxFrames || n_quotas < 1 || n_quotas > kMaxLadder) return ICER_INVALID_INPUT;
-    if (!quotas || !d_lens || !d_out || !d_sizes || !d_rcs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
-    LadderQuotas lq = {};
-    size_t top = 0;
-    for (int q = 0; q < n_quotas; q++) { lq.q[q] = quotas[q]; top = std::max(top, quotas[q]); }
-    if (out_stride < top) return ICER_INVALID_INPUT;
-    if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
-    const RecutLayout L = recut_layout(r, n, data_bytes, n_quotas);
-    if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
-    int rc = ICER_RESULT_OK;
-    uint8_t *ws = (uint8_t *)workspace;
-    AsyncHead *head = (AsyncHead *)(ws + L.head);
-    DCandRec *recs = (DCandRec *)(ws + L.cands);
-    uint32_t *tab_off = (uint32_t *)(ws + L.tab_off), *tab_bits = (uint32_t *)(ws + L.tab_bits), *bits = (uint32_t *)(ws + L.bits);
-    uint64_t *foff = (uint64_t *)(ws + L.foff);
-    const uint32_t blob_len = (uint32_t)data_bytes;
-
-    // 1. candidates over the blob
-    if ((rc = recut_blob_pass(r, L, ws, n, d_data, data_bytes, st)) != ICER_RESULT_OK) return rc;
-    // 2. per frame: packet table, unit bit counts, the quota walk at every quota
-    ICER_LAUNCH_ON(st, recut_plan_kernel, (unsigned)n, kRecutPlanThreads, kRecutWalkLds, d_data, blob_len,
-                   d_offsets, (uint64_t)stream_stride, d_lens, recs, head, r->geom, r->w, r->h, (const uint32_t *)r->unit_slot,
-                   (const uint32_t *)r->final_order, (const UnitDesc *)r->units, r->n_units, lq, (uint32_t)n_quotas, tab_off, tab_bits,
-                   bits, foff, (unsigned long long *)d_sizes, d_rcs);
-    HIP_TRY(hipGetLastError());
-    // 3. the kept packets
-    ICER_LAUNCH_ON(st, recut_gather_kernel, dim3(r->n_units, (unsigned)n), kRecutGatherThreads, 0, d_data, d_offsets, (uint64_t)stream_stride,
-                   r->geom, (const uint32_t *)r->unit_slot, r->n_units, tab_off, bits, foff, (uint32_t)n_quotas, d_out, out_stride);
-    HIP_TRY(hipGetLastError());
-done:
-    return rc;
-}
-
-int recut_cuts_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
-                     const uint64_t *d_lens, const int *reduces, const size_t *quotas, int n_cuts, uint8_t *d_out, size_t out_stride,
-                     uint64_t *d_sizes, int32_t *d_rcs, void *workspace, size_t workspace_bytes, hipStream_t st)
+                const uint64_t *d_lens, bool by_resolution, const int *reduces, const size_t *quotas, int n_cuts, uint8_t *d_out,
+                size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *workspace, size_t workspace_bytes, hipStream_t st)
 {
     g_error.clear();
     if (!r || n < 1 || n > kRecutMaxFrames || n_cuts < 1 || n_cuts > kMaxLadder) return ICER_INVALID_INPUT;
-    if (!reduces || !quotas || !d_lens || !d_out || !d_sizes || !d_rcs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
+    if ((by_resolution && !reduces) || !quotas || !d_lens || !d_out || !d_sizes || !d_rcs || !workspace || (data_bytes && !d_data))
+        return ICER_INVALID_INPUT;
     RecutCuts cuts = {};
     size_t top = 0;
     uint32_t used = 0;
     for (int c = 0; c < n_cuts; c++) {
-        if (reduces[c] < 0 || reduces[c] > r->max_reduce) return ICER_INVALID_INPUT;
-        cuts.quota[c] = quotas[c]; cuts.reduce[c] = (uint8_t)reduces[c];
-        used |= 1u << reduces[c];
+        const int reduce = by_resolution ? reduces[c] : 0;
+        if (reduce < 0 || reduce > r->max_reduce) return ICER_INVALID_INPUT;
+        cuts.quota[c] = quotas[c]; cuts.reduce[c] = (uint8_t)reduce;
+        used |= 1u << reduce;
         top = std::max(top, quotas[c]);
     }
     if (out_stride < top) return ICER_INVALID_INPUT;
     if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
-    const RecutLayout L = recut_layout(r, n, data_bytes, n_cuts, true);
+    const RecutLayout L = recut_layout(r, n, data_bytes, n_cuts, by_resolution);
     if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
-    // (every reduce 0: the byte-quota re-cut itself, whose workspace is a part of this one's)
-    if (used == 1u)
-        return recut_async(r, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, quotas, n_cuts, d_out, out_stride, d_sizes, d_rcs,
-                           workspace, workspace_bytes, st);
     int rc = ICER_RESULT_OK;
     uint8_t *ws = (uint8_t *)workspace;
-    uint32_t *tab_off = (uint32_t *)(ws + L.tab_off), *tab_bits = (uint32_t *)(ws + L.tab_bits);
+    uint32_t *tab_off = (uint32_t *)(ws + L.blob.tab_off), *tab_bits = (uint32_t *)(ws + L.blob.tab_bits);
     uint64_t *foff = (uint64_t *)(ws + L.foff);
+    const uint32_t n_full = r->red[0].n_units;
     RecutCutTables tabs = {};
     uint32_t at = 0;
     for (int k = 0; k <= r->max_reduce; k++) {
@@ -402,17 +202,19 @@ int recut_cuts_async(icerx_recutter *r, int n, const uint8_t *d_data, size_t dat
     }
 
     // 1. candidates over the blob
-    if ((rc = recut_blob_pass(r, L, ws, n, d_data, data_bytes, st)) != ICER_RESULT_OK) return rc;
+    if ((rc = enqueue_blob_stage(L.blob, ws, (size_t)n, r->geom.slots(), d_data, data_bytes, (const uint32_t *)r->crc, r->n_cus, st)) !=
+        ICER_RESULT_OK)
+        return rc;
     // 2. per frame: packet table, then every cut's walk with the tables of its geometry
-    ICER_LAUNCH_ON(st, recut_cuts_plan_kernel, (unsigned)n, kRecutPlanThreads, kRecutWalkLevelsLds, d_data, (uint32_t)data_bytes, d_offsets,
-                   (uint64_t)stream_stride, d_lens, (const DCandRec *)(ws + L.cands), (const AsyncHead *)(ws + L.head), r->geom, r->w, r->h,
-                   tabs, r->units_total, cuts, (uint32_t)n_cuts, used, tab_off, tab_bits, (uint32_t *)(ws + L.bits), foff,
-                   (uint64_t *)(ws + L.by_unit), (unsigned long long *)d_sizes, d_rcs);
+    ICER_LAUNCH_ON(st, recut_plan_kernel, (unsigned)n, kRecutPlanThreads, kWalkLds, d_data, (uint32_t)data_bytes, d_offsets,
+                   (uint64_t)stream_stride, d_lens, (const DCandRec *)(ws + L.blob.cands), (const AsyncHead *)(ws + L.blob.head), r->geom,
+                   r->w, r->h, tabs, L.bits_stride, cuts, (uint32_t)n_cuts, used, tab_off, tab_bits, (uint32_t *)(ws + L.bits), foff,
+                   by_resolution ? (uint64_t *)(ws + L.by_unit) : nullptr, (unsigned long long *)d_sizes, d_rcs);
     HIP_TRY(hipGetLastError());
     // 3. the kept packets, each with its cut's header
-    ICER_LAUNCH_ON(st, recut_cuts_gather_kernel, dim3(r->n_units, (unsigned)n), kRecutGatherThreads, 0, d_data, d_offsets,
-                   (uint64_t)stream_stride, r->geom, (const uint32_t *)r->unit_slot, r->n_units, tab_off, tab_bits, foff, cuts,
-                   (uint32_t)n_cuts, (const uint32_t *)r->crc, d_out, out_stride);
+    ICER_LAUNCH_ON(st, recut_gather_kernel, dim3(n_full, (unsigned)n), kRecutGatherThreads, 0, d_data, d_offsets, (uint64_t)stream_stride,
+                   r->geom, (const uint32_t *)r->red[0].unit_slot, n_full, tab_off, tab_bits, foff, cuts, (uint32_t)n_cuts,
+                   (const uint32_t *)r->crc, d_out, out_stride);
     HIP_TRY(hipGetLastError());
 done:
     return rc;
@@ -463,7 +265,6 @@ int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int ch
     icerx_recutter *r = new icerx_recutter;
     r->device = device; r->w = w; r->h = h; r->max_reduce = max_reduce;
     r->geom = DPlanGeom{(uint32_t)channels, (uint32_t)stages, segments, (uint32_t)(sample_bits == 8 ? kPlanes8 : kPlanes)};
-    r->n_units = (uint32_t)plans[0].units.size();
 #ifndef ICER_HOST_MOCK
     { int cur = 0; hipDeviceProp_t prop; if (hipGetDevice(&cur) == hipSuccess && hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) r->n_cus = prop.multiProcessorCount; }
 #endif
@@ -472,14 +273,12 @@ int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int ch
     int rc = ICER_RESULT_OK;
     std::vector<uint32_t> slot0, slot;
     HIP_TRY(recut_upload(&r->crc, crc_tab, sizeof crc_tab));
-    if ((rc = recut_upload_plan(plans[0], r->geom, 0, &slot0, &r->unit_slot, &r->final_order, &r->units)) != ICER_RESULT_OK) goto done;
-    r->red[0].n_units = r->n_units; r->red[0].unit_slot = r->unit_slot; r->red[0].final_order = r->final_order; r->red[0].units = r->units;
-    r->units_total = r->n_units;
-    for (int k = 1; k <= max_reduce; k++) {
+    for (int k = 0; k <= max_reduce; k++) {
         icerx_recutter::Reduced &g = r->red[k];
         g.n_units = (uint32_t)plans[k].units.size();
         r->units_total += g.n_units;
         if ((rc = recut_upload_plan(plans[k], r->geom, (uint32_t)k, &slot, &g.unit_slot, &g.final_order, &g.units)) != ICER_RESULT_OK) goto done;
+        if (k == 0) { slot0 = slot; continue; }
         std::vector<uint32_t> of_slot(r->geom.slots(), kNoPacket), full_to_cut(slot0.size());
         for (size_t u = 0; u < slot.size(); u++) of_slot[slot[u]] = (uint32_t)u;
         for (size_t u = 0; u < slot0.size(); u++) full_to_cut[u] = of_slot[slot0[u]];
@@ -499,9 +298,8 @@ extern "C" {
 void icerx_recutter_destroy(icerx_recutter *r)
 {
     if (!r) return;
-    for (void *p : {r->crc, r->unit_slot, r->final_order, r->units})
-        if (p) (void)hipFree(p);
-    for (int k = 1; k <= kRecutMaxReduce; k++)
+    if (r->crc) (void)hipFree(r->crc);
+    for (int k = 0; k <= kRecutMaxReduce; k++)
         for (void *p : {r->red[k].unit_slot, r->red[k].final_order, r->red[k].units, r->red[k].full_to_cut})
             if (p) (void)hipFree(p);
     delete r;
@@ -524,15 +322,15 @@ int icerx_recutter_max_reduce(const icerx_recutter *r) { return r ? r->max_reduc
 size_t icerx_recut_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_quotas)
 {
     if (!r || n <= 0 || n_quotas < 1 || n_quotas > kMaxLadder) return 0;
-    return recut_layout(r, n, data_bytes, n_quotas).total;
+    return recut_layout(r, n, data_bytes, n_quotas, false).total;
 }
 
 int icerx_recut_device_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
                              size_t stream_stride, const uint64_t *d_lens, const size_t *quotas, int n_quotas, uint8_t *d_out,
                              size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    return recut_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, quotas, n_quotas, d_out, out_stride,
-                       d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
+    return recut_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, false, nullptr, quotas, n_quotas, d_out,
+                       out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t icerx_recut_cuts_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts)
@@ -546,8 +344,8 @@ int icerx_recut_device_cuts_async(icerx_recutter *r, int n, const void *d_data, 
                                   uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *d_workspace,
                                   size_t workspace_bytes, void *stream)
 {
-    return recut_cuts_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, reduces, quotas, n_cuts, d_out,
-                            out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
+    return recut_async(r, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, true, reduces, quotas, n_cuts, d_out,
+                       out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ from tests.test_recut_mock import expected, mock_lib        # noqa: F401  (fixtu
 
 SENT, SENT_SIZE, SENT_RC = trm.SENT, trm.SENT_SIZE, trm.SENT_RC
 QUOTA_EXCEEDED, OUT_OF_DATA, INVALID_INPUT, FATAL = trm.QUOTA_EXCEEDED, trm.OUT_OF_DATA, trm.INVALID_INPUT, trm.FATAL
+GUARD = trm.GUARD
 
 # (w, h, channels, stages, filter, segments, bits) with the frame kinds of test_recut_mock.GEOMETRIES.  At 250 x 187 the uint8
 # frame ("noise6", 1) overflows in the transform (the oracle returns ICER_INTEGER_OVERFLOW and no stream): it stays as an
@@ -55,13 +56,14 @@ def cuts_call(r, blob, offsets, lens, cuts, stream_stride=0, stride=None, ws_byt
     ln = np.asarray(lens, np.uint64)
     keep = blob.copy()
     need = r.cuts_workspace_bytes(n, len(blob), Q)
-    work = np.full(max(need, 1), 0xCD, np.uint8)
+    work = np.full(need + GUARD, 0xCD, np.uint8)                        # (the call is handed `need` bytes; a guard tail behind them)
     args = dict(n=n, d_data=blob.ctypes.data, data_bytes=len(blob), d_offsets=offs.ctypes.data if offs is not None else None,
                 stream_stride=stream_stride, d_lens=ln.ctypes.data, reduces=reduces, quotas=quotas, d_out=out.ctypes.data,
                 out_stride=stride, d_sizes=sizes.ctypes.data, d_rcs=rcs.ctypes.data, d_workspace=work.ctypes.data,
                 workspace_bytes=need if ws_bytes is None else ws_bytes, stream=None)
     args.update(override)
     rc = r.recut_cuts_device_async_ptrs(**args)
+    assert (work[need:] == 0xCD).all(), "written behind the workspace"
     assert np.array_equal(blob, keep), "the masters were modified"
     if rc != 0:
         assert (out == SENT).all() and (sizes == SENT_SIZE).all() and (rcs == SENT_RC).all(), "a refused call wrote"
@@ -229,7 +231,7 @@ def test_reduce_0_is_the_existing_recut(mock_lib, expected, name):
     rc, want = trm.recut_call(plain, blob, offsets, lens, quotas)
     assert rc == 0
     r = recutter(mock_lib, g)
-    # all reduces 0, and reduce 0 next to another reduce (the call then takes the cuts' own kernels)
+    # all reduces 0, and reduce 0 next to another reduce
     for cuts in ([(0, q) for q in quotas], [(0, q) for q in quotas] + [(1, quotas[1])]):
         for rec in (r, plain) if cuts[-1][0] == 0 else (r,):
             rc, got = cuts_call(rec, blob, offsets, lens, cuts)
@@ -240,6 +242,24 @@ def test_reduce_0_is_the_existing_recut(mock_lib, expected, name):
     assert r.workspace_bytes(len(lens), len(blob), 4) == plain.workspace_bytes(len(lens), len(blob), 4)
     assert cuts_call(plain, blob, offsets, lens, [(0, quotas[0]), (1, quotas[1])])[0] == INVALID_INPUT, "a plain recutter refuses reduce 1"
     plain.close()
+    r.close()
+    if name != "gray8":
+        return
+    # the same entry point on test_recut_mock's gray8 geometry (256 x 192, several segments, the 8-bit final order), where the
+    # oracle's streams are the expected value: a recutter that holds reduced geometries works in the byte-quota call's own,
+    # smaller workspace (recut_call hands it just that much and checks the bytes behind it)
+    g, specs = trm.GEOMETRIES["gray8"]
+    mq = ebc.quota(g, "lossless")
+    masters = [expected(g, s, mq) for s in specs]
+    quotas = [ebc.quota(g, c) for c in ("lossless", "cut", "progressive", "tiny60")]
+    blob, offsets = trm.pack_odd(rng, [m[1] for m in masters])
+    r = recutter(mock_lib, g)
+    assert r.max_reduce == g.stages - 1 and r.workspace_bytes(len(masters), len(blob), 4) < r.cuts_workspace_bytes(len(masters), len(blob), 4)
+    rc, got = trm.recut_call(r, blob, offsets, [len(m[1]) for m in masters], quotas)
+    assert rc == 0
+    for q, quota in enumerate(quotas):
+        for f, spec in enumerate(specs):
+            ebc.check_frame(*got[q][f], trm.wanted(expected, g, spec, masters[f], mq, quota), f"quota {quota} frame {f} {spec}")
     r.close()
 
 

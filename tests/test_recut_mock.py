@@ -17,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SENT, SENT_SIZE, SENT_RC = 0xA5, 0x7777777777777777, 0x66666666
 QUOTA_EXCEEDED, OUT_OF_DATA, INVALID_INPUT, FATAL = -5, -7, -11, -10
+GUARD = 4096                                       # sentinel bytes behind the workspace a call is handed
 
 GEOMETRIES = {
     "yuv16": (ebc.Geometry(256, 192, 3, 3, 1, 5), [("smooth", 0), ("noise8", 1), ("blank", 0), (("sparse", "dot", "wide"), 2)]),
@@ -58,7 +59,7 @@ def recut_call(r, blob, offsets, lens, quotas, stream_stride=0, stride=None, ws_
     ln = np.asarray(lens, np.uint64)
     keep = blob.copy()
     need = r.workspace_bytes(n, len(blob), Q)
-    work = np.full(max(need, 1), 0xCD, np.uint8)
+    work = np.full(need + GUARD, 0xCD, np.uint8)                        # (the call is handed `need` bytes; a guard tail behind them)
     args = dict(n=n, d_data=blob.ctypes.data, data_bytes=len(blob), d_offsets=offs.ctypes.data if offs is not None else None,
                 stream_stride=stream_stride, d_lens=ln.ctypes.data, quotas=quotas, d_out=out.ctypes.data, out_stride=stride,
                 d_sizes=sizes.ctypes.data, d_rcs=rcs.ctypes.data, d_workspace=work.ctypes.data,
@@ -67,6 +68,7 @@ def recut_call(r, blob, offsets, lens, quotas, stream_stride=0, stride=None, ws_
         override["quotas"] = override.pop("quotas_arg")
     args.update(override)
     rc = r.recut_device_async_ptrs(**args)
+    assert (work[need:] == 0xCD).all(), "written behind the workspace"
     assert np.array_equal(blob, keep), "the masters were modified"
     if rc != 0:
         assert (out == SENT).all() and (sizes == SENT_SIZE).all() and (rcs == SENT_RC).all(), "a refused call wrote"
