@@ -85,6 +85,8 @@ def load_library() -> C.CDLL:
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icerx_encode_device_budget.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.icerx_encode_device_roi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.icerx_target_threshold.restype = C.c_uint64
     L.icerx_target_threshold.argtypes = [C.c_void_p, C.c_double]
     L.icerx_get_distortion_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -277,6 +279,37 @@ class Encoder:
         st = torch.cuda.current_stream(dev).cuda_stream
         self.encode_ladder_ptrs(frames.data_ptr(), n, quotas, out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(), st)
         return out, sizes, rcs
+
+    def encode_roi_ptrs(self, d_frames: int, n_frames: int, d_rois: int, shift: int, quotas, d_out: int, out_stride: int, d_sizes: int,
+                        d_rcs: int, d_kept: int, d_foreground: int, stream: int = 0) -> None:
+        """icerx_encode_device_roi: the ladder's call with every frame's quota spent first inside its rectangle (d_rois: device,
+        n_frames x 4 uint32 x, y, w, h), the foreground `shift` bit planes ahead; outputs quota-major as the ladder's, K to entry
+        q * n_frames + f of d_kept, the frames' foreground units to d_foreground"""
+        qs = [int(q) for q in quotas]
+        arr = (C.c_size_t * max(len(qs), 1))(*qs)
+        rc = self.lib.icerx_encode_device_roi(self.handle, d_frames, n_frames, d_rois, int(shift), arr, len(qs), d_out, out_stride, d_sizes,
+                                              d_rcs, d_kept, d_foreground, stream)
+        if rc != 0:
+            raise IcerHipError(f"icerx_encode_device_roi rc={rc}: {self.lib.icerx_last_error().decode()}")
+
+    def encode_roi_torch(self, frames, rois, shift: int, quotas):
+        """frames: as encode_ladder_torch takes them.  rois: cuda int32 or uint32 tensor (n, 4) on the frames' device -- x, y, w, h
+        of every frame's rectangle, read on torch's current stream (no synchronisation needed after the kernel that wrote it).
+        Returns cuda tensors (out uint8 (Q, n, largest quota), sizes int64 (Q, n), rcs int32 (Q, n), kept int32 (Q, n) holding the
+        uint32 K, foreground int32 (n,))."""
+        import torch
+        n, Q, dev = frames.shape[0], len(quotas), frames.device
+        if rois.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(rois.shape) != (n, 4) or rois.device != dev or \
+                not rois.is_contiguous():
+            raise ValueError("rois must be a contiguous int32 or uint32 tensor (n, 4) on the frames' device")
+        out = torch.empty((Q, n, max(int(q) for q in quotas)), dtype=torch.uint8, device=dev)
+        sizes = torch.empty((Q, n), dtype=torch.int64, device=dev)
+        rcs, kept = (torch.empty((Q, n), dtype=torch.int32, device=dev) for _ in range(2))
+        foreground = torch.empty((n,), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        self.encode_roi_ptrs(frames.data_ptr(), n, rois.data_ptr(), shift, quotas, out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(),
+                             kept.data_ptr(), foreground.data_ptr(), st)
+        return out, sizes, rcs, kept, foreground
 
     def encode_target_ptrs(self, d_frames: int, n_frames: int, targets_mse, byte_cap: int, d_out: int, out_stride: int, d_sizes: int,
                            d_rcs: int, d_reached: int, d_dist: int, d_equiv_quota: int, stream: int = 0) -> None:

@@ -168,6 +168,7 @@ struct Ladder {
     int pitch = 0;          // frames of the call: the rows of one quota's block of the output
 };
 static_assert(kMaxLadder == ICERX_MAX_LADDER, "assemble_ladder.hpp and include/icer_hip.h agree on the ladder's length");
+static_assert(kMaxRoiShift == ICERX_MAX_ROI_SHIFT, "roi_core.hpp and include/icer_hip.h agree on the largest shift");
 
 // The targets of a quality-targeted call (icerx_encode_device_target): the batch is planned and coded as a call at the byte cap, and
 // each target's stream is cut from it where the target is met (distortion_core.hpp).  Output rows are target-major, as a ladder's.
@@ -190,6 +191,17 @@ struct Budget {
     unsigned long long *d_dist = nullptr, *d_equiv = nullptr, *d_threshold = nullptr, *d_total = nullptr;
 };
 
+// A region-of-interest call (icerx_encode_device_roi): a ladder call -- planned and coded for the largest quota, with every unit coded --
+// whose streams are cut along each frame's ROI order (roi_core.hpp).  Output rows are quota-major.  Every pointer is of the call's first frame.
+struct Roi {
+    LadderQuotas quotas;
+    int n = 0;              // quotas
+    int pitch = 0;          // frames of the call
+    uint32_t shift = 0;
+    const uint32_t *d_rois = nullptr;               // per frame: x, y, w, h
+    uint32_t *d_kept = nullptr, *d_foreground = nullptr;
+};
+
 // One encode call, as every layer between the C ABI and the kernels takes it: device pointers of its first frame, everything on `stream`.
 struct EncodeCall {
     const uint16_t *d_frames; int n_frames; size_t quota;               // (a ladder call: its largest quota)
@@ -200,10 +212,11 @@ struct EncodeCall {
                                         // stack of icerx_encode_device_ladder, a synchronous call: a call left in icerx_encoder::Pending never has one
     const Target *target = nullptr;     // a quality-targeted call (quota = its byte cap): the same, on the stack of icerx_encode_device_target
     const Budget *budget = nullptr;     // a budget call (quota = its byte cap): the same, on the stack of icerx_encode_device_budget
+    const Roi *roi = nullptr;           // a region-of-interest call (quota = its largest quota): the same, on the stack of icerx_encode_device_roi
     // the same call for its frames [f0, f0 + n), `frame_elems` samples each
     EncodeCall frames(int f0, int n, size_t frame_elems) const
     {
-        return EncodeCall{d_frames + (size_t)f0 * frame_elems, n, quota, d_out + (size_t)f0 * out_stride, out_stride, d_sizes + f0, d_rcs + f0, stream, overlap_ok, ladder, target, budget};
+        return EncodeCall{d_frames + (size_t)f0 * frame_elems, n, quota, d_out + (size_t)f0 * out_stride, out_stride, d_sizes + f0, d_rcs + f0, stream, overlap_ok, ladder, target, budget, roi};
     }
 };
 
@@ -271,6 +284,12 @@ struct icerx_encoder {
     DevBuf<unsigned long long> curve;   // D_k, then used_k: 2 x max_frames x (units + 1)
     DevBuf<uint32_t> curve_head;        // max_frames x kCurveHeadWords
     DevBuf<BudgetState> budget_state;   // the search's scratch for calls of more than kBudgetLdsFrames frames: kMaxLadder x max_frames
+
+    // region-of-interest calls (roi_core.hpp): made by the first icerx_encode_device_roi, nothing before
+    DevBuf<uint64_t> roi_prio;          // the priority of every unit's packet
+    DevBuf<uint64_t> roi_keys;          // roi_rank_kernel's scratch: max_frames x units
+    DevBuf<uint32_t> roi_rank, roi_order;   // max_frames x units
+    DevBuf<uint32_t> roi_bits;          // scan_roi_kernel's scratch, laid out as final_off: quotas x max_frames x units
 
     int *h_flag = nullptr;              // pinned host words: slot-bound overflow flag of the last batch, units on its route list
     hipEvent_t done = nullptr;          // end of the last batch on its stream
@@ -527,6 +546,7 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
     unsigned long long *const d_sizes = reinterpret_cast<unsigned long long *>(c.d_sizes);
     const size_t quota = c.quota, out_stride = c.out_stride;
     const hipStream_t st = c.stream; const Ladder *const ladder = c.ladder; const Target *const target = c.target; const Budget *const budget = c.budget;
+    const Roi *const roi = c.roi;
     const bool energy = target || budget;       // the call cuts by distortion: it needs the families' residual energies
     const bool progressive = lp.progressive, use_wg = lp.use_wg, split = pp.split, hybrid = pp.hybrid;
     const size_t W = e->w, H = e->h, plane = W * H;
@@ -687,6 +707,16 @@ int enqueue_part(icerx_encoder *e, const LaunchPlan &lp, int part, bool timed, c
                            e->fam_weight.p, e->plan.n_families, tgt_planes, e->fam_ll_term.p, e->fam_chan.p, means, C, target->d_reached + f0, target->d_dist + f0, target->d_equiv + f0);
         hipLaunchKernelGGL(gather_ladder_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
                            e->units.p, n_units, unit_bits, final_off, off_pitch, (uint32_t)target->n, d_out, out_stride, (uint32_t)target->pitch);
+    } else if (roi) {
+        // the frames' ROI orders from their rectangles, then the ladder's scan along them; the gather is the ladder's
+        const size_t off_pitch = (size_t)e->max_frames * n_units;
+        uint32_t *const rank = e->roi_rank.p + (size_t)f0 * n_units, *const order = e->roi_order.p + (size_t)f0 * n_units;
+        hipLaunchKernelGGL(roi_rank_kernel, dim3(n_frames), dim3(64 * kRoiWaves), 0, st, e->units.p, n_units, e->roi_prio.p, roi->d_rois + 4 * (size_t)f0,
+                           roi->shift, (uint32_t)W, (uint32_t)H, e->roi_keys.p + (size_t)f0 * n_units, rank, order, roi->d_foreground + f0);
+        hipLaunchKernelGGL(scan_roi_kernel, dim3(n_frames, roi->n), dim3(64), 0, st, unit_bits, e->final_order.p, n_units, roi->quotas, skip, rank, order,
+                           e->roi_bits.p + (size_t)f0 * n_units, final_off, off_pitch, d_sizes, d_rcs, roi->d_kept + f0, (uint32_t)roi->pitch, e->units.p, bound_ovf);
+        hipLaunchKernelGGL(gather_ladder_kernel, dim3(n_units, n_frames), dim3(256), 0, st, slots, e->plan.slot_bytes,
+                           e->units.p, n_units, unit_bits, final_off, off_pitch, (uint32_t)roi->n, d_out, out_stride, (uint32_t)roi->pitch);
     } else if (!ladder || ladder->n == 1) {
         hipLaunchKernelGGL(scan_kernel, dim3(n_frames), dim3(64), 0, st, unit_bits, e->final_order.p, n_units,
                            (uint64_t)quota, skip, final_off, d_sizes, d_rcs, e->units.p, bound_ovf);
@@ -718,7 +748,7 @@ int enqueue(icerx_encoder *e, const EncodeCall &c, bool overlap_ok)
 {
     const hipStream_t st = c.stream;
     const CoderState cs{e->wg_available, e->wg_once, e->half_stream != nullptr};
-    const LaunchPlan &lp = e->last_plan = plan_launch(launch_shape(e), e->tuning, cs, c.n_frames, c.quota, overlap_ok);
+    const LaunchPlan &lp = e->last_plan = plan_launch(launch_shape(e), e->tuning, cs, c.n_frames, c.quota, overlap_ok, c.roi != nullptr);
     if (lp.n_parts == 1) return enqueue_part(e, lp, 0, true, c, true);
     HIP_TRY(hipMemsetAsync(e->bound_ovf(), 0, sizeof(int), st));        // (shared by the parts: before the second stream forks off)
     HIP_TRY(hipEventRecord(e->part_fork, st));                          // (the second stream starts behind whatever the caller's stream holds)
@@ -855,6 +885,7 @@ void icerx_encoder_destroy(icerx_encoder *e)
     e->subs.release(); e->sub_order.release(); e->snap_valid.release(); e->snaps.release(); e->sub_recs.release();
     e->dist.release(); e->fam_weight.release(); e->fam_chan.release(); e->fam_ll_term.release();
     e->curve.release(); e->curve_head.release(); e->budget_state.release();
+    e->roi_prio.release(); e->roi_keys.release(); e->roi_rank.release(); e->roi_order.release(); e->roi_bits.release();
     for (auto &ev : e->energy_fork) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : e->energy_join) if (ev) (void)hipEventDestroy(ev);
     for (auto &ev : e->ev) if (ev) (void)hipEventDestroy(ev);
@@ -1125,6 +1156,59 @@ int icerx_encode_device_ladder(icerx_encoder *e, const void *d_frames, int n_fra
         planes = e->in.p;
     }
     EncodeCall c{planes, n_frames, top, d_out, out_stride, d_sizes, d_rcs, st, true, &lq};
+    return encode_sync(e, c, caller_rows);
+}
+
+// Region-of-interest encode (include/icer_hip.h): checked in full before anything is enqueued, as the ladder is; then a synchronous call at
+// the largest quota, planned with every unit coded, whose assembly cuts every quota's streams along the frames' ROI orders.  What the
+// first such call of an encoder makes: the units' priorities on the device and the rank arrays.
+static int prepare_roi(icerx_encoder *e, int n_quotas)
+{
+    const size_t n_units = e->plan.units.size(), per_call = (size_t)e->max_frames * n_units;
+    if (!e->roi_prio.p) {
+        std::vector<uint64_t> prio;
+        if (!roi_priorities(e->plan, &prio)) {         // (no geometry the planner accepts gets here: make_packets keeps the bound and the order)
+            set_error("icerx_encode_device_roi: the packet priorities of this geometry do not fit the sort keys");
+            return ICER_FATAL_ERROR;
+        }
+        if (e->roi_keys.ensure(per_call) || e->roi_rank.ensure(per_call) || e->roi_order.ensure(per_call)) return ICER_FATAL_ERROR;
+        DevBuf<uint64_t> p;
+        if (p.ensure(n_units)) return ICER_FATAL_ERROR;
+        if (hipMemcpy(p.p, prio.data(), n_units * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) { p.release(); set_error("icerx_encode_device_roi: uploading the priorities failed"); return ICER_FATAL_ERROR; }
+        e->roi_prio = p;            // (last: its presence says that everything above exists)
+    }
+    if (e->roi_bits.ensure((size_t)n_quotas * per_call) || e->final_off.ensure((size_t)n_quotas * per_call)) return ICER_FATAL_ERROR;
+    return 0;
+}
+
+int icerx_encode_device_roi(icerx_encoder *e, const void *d_frames, int n_frames, const uint32_t *d_rois, int shift, const size_t *quotas, int n_quotas,
+                            uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, uint32_t *d_kept, uint32_t *d_foreground, void *stream)
+{
+    if (int rc = enter_encode("icerx_encode_device_roi", e, d_frames && d_rois && quotas && d_out && d_sizes && d_rcs && d_kept && d_foreground &&
+                              n_quotas >= 1 && n_quotas <= ICERX_MAX_LADDER && shift >= 0 && shift <= ICERX_MAX_ROI_SHIFT, n_frames, 0, 0,
+                              " (1 <= n_quotas <= ICERX_MAX_LADDER, 0 <= shift <= ICERX_MAX_ROI_SHIFT, 1 <= n_frames <= max_frames)")) return rc;
+    Roi rq;
+    rq.n = n_quotas;
+    rq.pitch = n_frames;
+    rq.shift = (uint32_t)shift;
+    rq.d_rois = d_rois;
+    rq.d_kept = d_kept;
+    rq.d_foreground = d_foreground;
+    size_t top = 0;
+    for (int q = 0; q < n_quotas; q++) { rq.quotas.q[q] = quotas[q]; top = std::max(top, quotas[q]); }
+    hipStream_t st = (hipStream_t)stream;
+    if (upload_units(e, top, st)) return ICER_FATAL_ERROR;
+    if (!stride_admissible(e, out_stride, top)) {
+        set_error("icerx_encode_device_roi: out_stride %zu smaller than the largest byte quota %zu", out_stride, top);
+        return ICER_INVALID_INPUT;
+    }
+    if (int rc = prepare_roi(e, n_quotas)) return rc;
+    const uint16_t *planes = static_cast<const uint16_t *>(d_frames);
+    if (e->sample_bits == 8) {          // (as icerx_encode_device_s8)
+        if (convert_samples(e, Convert::S8, static_cast<const uint8_t *>(d_frames), (size_t)n_frames * e->channels * e->w * e->h, st)) return ICER_FATAL_ERROR;
+        planes = e->in.p;
+    }
+    EncodeCall c{planes, n_frames, top, d_out, out_stride, d_sizes, d_rcs, st, true, nullptr, nullptr, nullptr, &rq};
     return encode_sync(e, c, caller_rows);
 }
 

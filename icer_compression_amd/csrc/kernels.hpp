@@ -6,6 +6,7 @@
 //   code_units_kernel                   context modeller + entropy coder + framing (a-9..a-15)
 //   scan_kernel / gather_kernel         quota cut + final stream order (a-16, a-17)
 //   scan_ladder_kernel / gather_ladder_kernel   the same at several quotas over one coded batch (assemble_ladder.hpp)
+//   roi_rank_kernel / scan_roi_kernel           the ladder's scan along a per-frame order that puts a rectangle first (roi_core.hpp)
 //   family_energy_kernel / scan_target_kernel   the cut where a distortion target is met (distortion_core.hpp)
 //   curve_kernel / budget_search_kernel         the cuts that share one byte budget at equal distortion (budget_core.hpp)
 // HBM layout: planes are row-major int16/uint16 with row stride = image width; plane p of a batch
@@ -15,6 +16,7 @@
 
 #include "assemble_core.hpp"
 #include "assemble_ladder.hpp"
+#include "roi_core.hpp"
 #include "coder_core.hpp"
 #include "distortion_core.hpp"
 #include "budget_core.hpp"
@@ -830,6 +832,47 @@ gather_ladder_kernel(const uint8_t *__restrict__ slots, size_t slot_frame_stride
     const uint32_t len = kHeaderBytes + ((unit_bits[(size_t)frame * n_units + ui] + 7u) >> 3);
     copy_unit_ladder(slots + (size_t)frame * slot_frame_stride + units[ui].slot_off, len, offs, off_pitch, n_q,
                      out + (size_t)frame * out_stride, (size_t)pitch * out_stride, threadIdx.x, 256u);
+}
+
+// ------------------------------------------------------------------------------------------ region of interest
+// The ladder's streams cut along a per-frame ROI order instead of the priority order (icerx_encode_device_roi); outputs and
+// final offsets laid out as the ladder's, so gather_ladder_kernel takes them unchanged.
+
+// rank[frame][u], order[frame][i] and the foreground units of every frame from the frame's rectangle rois[4 * frame ..] = x, y,
+// w, h.  `keys`: n_units words of scratch per frame.  grid = frames, block = 64 * kRoiWaves.
+__global__ void __launch_bounds__(64 * kRoiWaves)
+roi_rank_kernel(const UnitDesc *__restrict__ units, uint32_t n_units, const uint64_t *__restrict__ prio, const uint32_t *__restrict__ rois,
+                uint32_t shift, uint32_t img_w, uint32_t img_h, uint64_t *keys, uint32_t *__restrict__ rank, uint32_t *__restrict__ order,
+                uint32_t *__restrict__ foreground)
+{
+    __shared__ RoiShared s;
+    const uint32_t frame = blockIdx.x, wv = threadIdx.x >> 6;
+    const RoiFrame f{units, n_units, img_w, img_h, roi_clip(rois + 4u * frame, img_w, img_h)};
+    uint64_t *k = keys + (size_t)frame * n_units;
+    roi_count_wave(s, f, wv, (uint32_t)kRoiWaves);
+    __syncthreads();
+    if (wv == 0) roi_scan_wave(s, n_units);
+    __syncthreads();
+    roi_place_wave(s, f, prio, shift, k, nullptr, nullptr, wv, (uint32_t)kRoiWaves);
+    __syncthreads();
+    roi_place_wave(s, f, prio, shift, k, rank + (size_t)frame * n_units, order + (size_t)frame * n_units, wv, (uint32_t)kRoiWaves);
+    if (threadIdx.x == 0) foreground[frame] = s.n_fg;
+}
+
+// One wavefront per (frame, quota): scan_ladder_kernel along the frame's ROI order.  `pbits`: the scratch of scan_roi_wave, laid
+// out as final_off; `kept`: rows as sizes / rcs.  grid = (frames, quotas), block = 64.
+__global__ void __launch_bounds__(64)
+scan_roi_kernel(const uint32_t *__restrict__ unit_bits, const uint32_t *__restrict__ final_order, uint32_t n_units, LadderQuotas quotas,
+                const int *__restrict__ frame_skip, const uint32_t *__restrict__ rank, const uint32_t *__restrict__ order, uint32_t *pbits,
+                uint64_t *__restrict__ final_off, size_t off_pitch, unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs,
+                uint32_t *__restrict__ kept, uint32_t pitch, const UnitDesc *__restrict__ units, int *__restrict__ bound_overflow)
+{
+    const uint32_t frame = blockIdx.x, q = blockIdx.y;
+    const size_t row = (size_t)q * pitch + frame, at = (size_t)q * off_pitch + (size_t)frame * n_units;
+    const uint32_t flags = scan_roi_wave(unit_bits + (size_t)frame * n_units, final_order, n_units, quotas.q[q], frame_skip[frame], units,
+                                         rank + (size_t)frame * n_units, order + (size_t)frame * n_units, pbits + at, final_off + at, sizes + row,
+                                         rcs + row, kept + row);
+    if (flags && threadIdx.x == 0) atomicOr(bound_overflow, (int)flags);
 }
 
 // ------------------------------------------------------------------------------------------ distortion target

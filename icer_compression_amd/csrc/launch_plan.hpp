@@ -93,8 +93,10 @@ inline bool plans_sub_ranges(const LaunchShape &s, const Tuning &t, bool wg_avai
 // Whether an encoder gets the stream of a batch's odd parts (api.hip create_part_events): batches of four frames or more can be parts.
 inline bool wants_half_stream(const LaunchShape &s, const Tuning &t) { return s.max_frames >= 4 && t.overlap_parts > 1; }
 
-// `overlap_ok`: the call may be enqueued in parts on two streams (the synchronous entry points)
-inline LaunchPlan plan_launch(const LaunchShape &s, const Tuning &t, const CoderState &st, int n_frames, size_t quota, bool overlap_ok)
+// `overlap_ok`: the call may be enqueued in parts on two streams (the synchronous entry points).  `code_all`: the call's cut is not a
+// prefix of the priority order (a region-of-interest call), so every unit is coded whatever the quota: never progressive mode.
+inline LaunchPlan plan_launch(const LaunchShape &s, const Tuning &t, const CoderState &st, int n_frames, size_t quota, bool overlap_ok,
+                              bool code_all = false)
 {
     LaunchPlan p;
     const int C = s.channels;
@@ -102,7 +104,7 @@ inline LaunchPlan plan_launch(const LaunchShape &s, const Tuning &t, const Coder
     // the stream.  The units are then launched in priority order with the quota: a unit whose finished higher-priority
     // predecessors alone already exceed it stops (at its start, or at its next check) -- see quota_already_spent.  Not used
     // for large quotas, where the launch order is largest-first instead.
-    p.progressive = quota < s.w * s.h * C / 2;
+    p.progressive = !code_all && quota < s.w * s.h * C / 2;
     p.use_wg = st.wg_available && (st.wg_once || t.coder == 2 || (t.coder == 0 && p.progressive));
     // Both coders in one launch: the bit planes that are mostly runs of blank chunks go to the list kernel (the window coder,
     // which closes such runs in closed form), the dense ones to the pipeline (route_units_kernel).  A launch of very few planes

@@ -224,6 +224,49 @@ int icerx_encode_device_budget(icerx_encoder *enc, const void *d_frames, int n_f
                                int32_t *d_at_cap, uint64_t *d_dist, uint64_t *d_equiv_quota, uint64_t *d_threshold,
                                uint64_t *d_total, void *stream);
 
+/* Region-of-interest encode: a rate ladder whose byte quotas are spent inside a rectangle first.  Every other cut of this
+ * library is a prefix of ICER's priority order, which spreads the bytes evenly over the picture.  The format allows more: a
+ * packet names its own (channel, level, subband, bit plane, segment), a decoder files the packets it finds by those fields and
+ * decodes each segment from its top plane down until one is missing, so a stream that keeps more bit planes of some segments
+ * than of others is an ordinary ICER stream.  This call chooses WHICH packets are kept, never what a packet holds: every
+ * output is a subset of the packets of the frame's lossless stream, byte for byte, in the usual final order.
+ * The rule (tests/roi_model.py states it in plain integers; DESIGN.md 3 "Region of interest"):
+ *   - a frame's rectangle (x, y, w, h) is read as uint32 and clipped to the frame: [x0, x1) x [y0, y1);
+ *   - a coding unit of level l whose rectangle in its subband's own coordinates is [sx, sx + sw) x [sy, sy + sh) is FOREGROUND
+ *     when it belongs to the LL subband (in every frame, so that the background stays a picture), or when the clipped
+ *     rectangle is not empty and  sx < ceil(x1 / 2^l) + 2,  sx + sw + 2 > floor(x0 / 2^l)  and the same two hold in y
+ *     (a guard of 2 coefficients).  All bit planes of a (channel, level, subband, segment) share a rectangle;
+ *   - eff = priority << shift for foreground units, the packet's priority for the others; the ROI order sorts the units by eff
+ *     descending, ties in priority order.  Within a family the planes stay in descending order: no hole above a kept plane.
+ *     A frame whose clipped rectangle is empty has no region of interest: its shift is 0 and its order the priority order
+ *     (with LL alone shifted, "no rectangle" would not be the plain stream);
+ *   - the quota walk of icerx_encode_device (a unit is kept iff its 28 header bytes fit and floor(bits / 8) < quota - used -
+ *     28; the first unit that fails ends the walk) runs over the units in ROI order and keeps the first K of it.
+ * So shift = 0, an empty rectangle, one outside the frame, one whose foreground is every unit, and any encoder of one segment
+ * give exactly icerx_encode_device_ladder's streams, and a quota that keeps every unit gives the lossless stream.
+ *   d_frames     as icerx_encode_device_ladder takes them; not modified
+ *   d_rois       DEVICE pointer, n_frames x 4 uint32: x, y, w, h of each frame's rectangle, read on `stream` (a tensor of
+ *                boxes that a detector wrote on the same stream goes straight in; int32 values below 0 read as far outside)
+ *   shift        0 <= shift <= ICERX_MAX_ROI_SHIFT: how many bit planes the foreground is put ahead
+ *   quotas, d_out, out_stride, d_sizes, d_rcs   as the ladder's, quota-major; rc ICER_BYTE_QUOTA_EXCEEDED when K is less than
+ *                the frame's units, else ICER_RESULT_OK
+ *   d_kept       device pointer, n_quotas * n_frames uint32, entry q * n_frames + f: K
+ *   d_foreground device pointer, n_frames uint32: the frame's foreground units
+ * A frame without a stream (ICER_INTEGER_OVERFLOW) has size 0 and K 0.  Synchronous, with the same re-runs as the ladder.
+ * Cost: a ROI cut is not a priority prefix, so the call codes EVERY unit whatever the quotas (the ladder stops coding once a
+ * small largest quota is spent): at a small quota it costs about what a lossless call costs (profiles/roi.md).  Slots are
+ * sized from the largest quota as for the ladder -- a unit that outgrows a quota-sized slot fits the stream in no order.
+ * icerx_recut_device_async treats a ROI stream like a damaged one: a unit without a packet ends its walk, so a re-cut keeps
+ * the priority prefix that is whole and drops what the ROI order had kept beyond it.
+ * Returns 0, ICER_INVALID_INPUT (nothing enqueued or written: what the ladder refuses, a null d_rois, d_kept or d_foreground,
+ * a shift outside 0 .. ICERX_MAX_ROI_SHIFT) or ICER_FATAL_ERROR (HIP failure).  The rank arrays live in encoder-owned device
+ * memory made by the first such call -- 16 bytes per unit and frame, and 4 more per quota --; an encoder that never makes one pays
+ * nothing. */
+#define ICERX_MAX_ROI_SHIFT 16
+int icerx_encode_device_roi(icerx_encoder *enc, const void *d_frames, int n_frames, const uint32_t *d_rois, int shift,
+                            const size_t *quotas, int n_quotas, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes,
+                            int32_t *d_rcs, uint32_t *d_kept, uint32_t *d_foreground, void *stream);
+
 /* The same call in two halves.  icerx_encode_device_async returns as soon as all work is enqueued on `stream`;
  * icerx_encoder_wait returns once it has completed there (re-running the batch in the rare cases the synchronous call
  * does: a coding unit that outgrew its slot, a unit time-out).  Between the two the caller may enqueue its own copies
