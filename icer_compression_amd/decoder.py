@@ -66,6 +66,13 @@ def bind(path: str) -> C.CDLL:
         lib.icerx_recut_device_cuts_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_int),
                                                       C.POINTER(_sz), C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
                                                       C.c_void_p]
+    # re-cutting by region of interest, at any resolution
+    if hasattr(lib, "icerx_recut_device_roi_async"):
+        lib.icerx_recut_roi_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, C.c_int]
+        lib.icerx_recut_roi_workspace_bytes.restype = _sz
+        lib.icerx_recut_device_roi_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz), C.c_int, C.c_void_p, _sz,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
     return lib
 
 
@@ -392,6 +399,7 @@ class Recutter:
                                                C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
         self._workspaces = {}                # recut_torch: one cached workspace per torch stream
         self._cuts_workspaces = {}           # recut_cuts_torch: the same, sized for the cuts call
+        self._roi_workspaces = {}            # recut_roi_torch: the same, sized for the ROI call
         self.handle = C.c_void_p()
         self.max_reduce = 0
         if max_reduce != 0:
@@ -411,6 +419,7 @@ class Recutter:
             self.handle = C.c_void_p()
         self._workspaces.clear()
         self._cuts_workspaces.clear()
+        self._roi_workspaces.clear()
 
     def __del__(self):
         try:
@@ -556,6 +565,65 @@ class Recutter:
         torch.cuda.current_stream(dev).synchronize()
         out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
         return [[(int(rcs[c * n + f]), out[c * n + f, : int(sizes[c * n + f])].tobytes()) for f in range(n)] for c in range(Q)]
+
+    # ---- cuts by region of interest, at any resolution (icerx_recut_device_roi_async) ----
+    def roi_workspace_bytes(self, n: int, data_bytes: int, n_cuts: int) -> int:
+        """icerx_recut_roi_workspace_bytes: the device workspace one recut_roi_device_async_ptrs call needs"""
+        return int(_need(self.lib, "icerx_recut_roi_workspace_bytes")(self.handle, n, data_bytes, n_cuts))
+
+    def recut_roi_device_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, d_rois: int,
+                                    reduces, shifts, quotas, d_out: int, out_stride: int, d_sizes: int, d_rcs: int, d_kept: int,
+                                    d_foreground: int, d_workspace: int, workspace_bytes: int, stream: int = 0, n_cuts=None) -> int:
+        """icerx_recut_device_roi_async on raw device pointers (arguments as recut_cuts_device_async_ptrs; d_rois: n x 4 uint32
+        x, y, w, h in device memory; reduces, shifts and quotas: host sequences of one length, None for a null pointer --
+        reduces None: every reduce 0; d_kept / d_foreground: uint32, entry c * n + f as d_sizes).  Enqueues on `stream` and
+        returns the call's rc without waiting."""
+        fn = _need(self.lib, "icerx_recut_device_roi_async")
+        red = None if reduces is None else (C.c_int * max(len(reduces), 1))(*[int(r) for r in reduces])
+        shf = None if shifts is None else (C.c_int * max(len(shifts), 1))(*[int(x) for x in shifts])
+        arr = None if quotas is None else (_sz * max(len(quotas), 1))(*[int(q) for q in quotas])
+        nc = n_cuts if n_cuts is not None else (len(quotas) if quotas is not None else 0)
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_rois, red, shf, arr, nc, d_out, out_stride,
+                  d_sizes, d_rcs, d_kept, d_foreground, d_workspace, workspace_bytes, stream)
+
+    def recut_roi_torch(self, data, lens, rois, cuts, out, sizes, rcs, kept, foreground, offsets=None, stream_stride=None) -> None:
+        """recut_cuts_torch with cuts = [(reduce, quota, shift), ...] and a rectangle per frame: rois, a cuda int32 / uint32 tensor
+        (n, 4) of x, y, w, h in pixels of the full frame, read on torch's current stream (write it there with any torch op
+        just before; nothing waits).  Row and entry c * n + f hold frame f at cuts[c]: the stream of the image at 1/2^reduce
+        size whose byte quota is spent inside the rectangle first; kept / foreground: cuda int32 of Q * n entries (the uint32
+        K and foreground units).  out[c] / sizes[c] go into decode_torch of a Decoder made for stages - reduce as they are.
+        Everything else as recut_cuts_torch; the workspace is cached per stream, apart from the other calls'."""
+        import torch
+        n, Q = int(lens.shape[0]), len(cuts)
+        if offsets is None and stream_stride is None:
+            if data.dim() != 2:
+                raise ValueError("a 1-D blob needs offsets or stream_stride")
+            stream_stride = data.stride(0)
+        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8),
+                            ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32), ("kept", kept, torch.int32),
+                            ("foreground", foreground, torch.int32)) + \
+                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
+                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        if not rois.is_cuda or not rois.is_contiguous() or rois.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or \
+                tuple(rois.shape) != (n, 4):
+            raise ValueError("rois: a contiguous cuda int32 / uint32 tensor (n, 4) is needed")
+        if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or any(t.numel() != Q * n for t in (sizes, rcs, kept, foreground)):
+            raise ValueError("out must be (Q * n, out_stride), sizes, rcs, kept and foreground Q * n entries")
+        st = torch.cuda.current_stream(data.device)
+        need = self.roi_workspace_bytes(n, data.numel(), Q)
+        work = self._roi_workspaces.get(st.cuda_stream)
+        if work is None or work.numel() < max(need, 1):
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
+            self._roi_workspaces[st.cuda_stream] = work
+        work.record_stream(st)
+        rc = self.recut_roi_device_async_ptrs(n, data.data_ptr(), data.numel(), offsets.data_ptr() if offsets is not None else None,
+                                              int(stream_stride or 0), lens.data_ptr(), rois.data_ptr(), [c[0] for c in cuts],
+                                              [c[2] for c in cuts], [c[1] for c in cuts], out.data_ptr(), out.shape[-1],
+                                              sizes.data_ptr(), rcs.data_ptr(), kept.data_ptr(), foreground.data_ptr(), work.data_ptr(),
+                                              work.numel(), st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_recut_device_roi_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
 
 
 # ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------

@@ -290,6 +290,61 @@ int icerx_recut_device_cuts_async(icerx_recutter *r, int n, const void *d_data, 
                                   int n_cuts, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs,
                                   void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Re-cutting by region of interest, at any resolution ---------------------------------------------------------------
+ * icerx_encode_device_roi (icer_hip.h) spends a byte quota inside a rectangle first, but it needs the frame.  The rule only
+ * chooses which packets are kept, so it can be applied to a stored master instead: a CUT is here a triple (reduce r, byte
+ * quota Q, ROI shift), each frame has a rectangle (x, y, w, h in pixels of the FULL frame), and
+ *   at r = 0 the cut of a master M is the region-of-interest rule of icer_hip.h run on M's packet table instead of the
+ *     coder's bit counts: walk M with the decoder's cursor rule exactly as icerx_recut_device_async does (every CRC-valid
+ *     packet takes part, the last packet of a kind wins, the master's two per-frame checks apply); a unit without a packet
+ *     "does not fit"; a unit is foreground when it belongs to LL or comes within 2 coefficients of the rectangle scaled to
+ *     its level; the units are ordered by eff = prio << shift (foreground) or prio (the others), descending, ties by unit
+ *     index; a frame whose rectangle, clipped to the frame, is empty has shift 0; the quota walk runs over that order and
+ *     keeps the first K units, which are copied verbatim in final order.
+ *   at r > 0 take [x0, x1) x [y0, y1), the frame's rectangle clipped to the full frame.  If it is empty the frame has no
+ *     region of interest at any r.  Otherwise the rectangle of the cut is [x0 >> r, ceil(x1 / 2^r)) x [y0 >> r,
+ *     ceil(y1 / 2^r)): never empty, and inside ceil(w / 2^r) x ceil(h / 2^r).  The cut is DEFINED as the r = 0 rule applied to
+ *     the derived stream M_r, with that rectangle and the same shift and quota, by a recutter made for
+ *     (ceil(w / 2^r), ceil(h / 2^r), channels, stages - r, segments, sample_bits): priority order, final order and priorities
+ *     are that geometry's own, and the headers are relabelled as in icerx_recut_device_cuts_async.
+ *     Since floor((x0 >> r) / 2^l) = floor(x0 / 2^(l + r)), and the same for the ceilings, a non-LL unit of level l at
+ *     1/2^r size is foreground exactly when the master's unit of level l + r is; only LL and the priorities differ.
+ * Consequences:
+ *   - r = 0 and a complete master: bytes, size, return code, K and the foreground count of icerx_encode_device_roi on the
+ *     original frame with the same rectangle, shift and quota.
+ *   - shift 0, a rectangle that is empty once clipped (one outside the frame included), a rectangle whose foreground is
+ *     every unit, or a one-segment geometry: icerx_recut_device_cuts_async's output for (r, Q), byte for byte.
+ *   - cuts compose: a stored ROI stream made with (rectangle, shift) at Q1, re-cut with the same rectangle and shift at
+ *     Q2 <= Q1, is the ROI stream at Q2; a stored output of cut (r, Q1, shift), re-cut by a plain recutter of the geometry
+ *     at 1/2^r size with the scaled rectangle at Q2 <= Q1, is cut (r, Q2, shift).
+ *   - a cut master, or one damaged above level r, ends the walk at the first unit IN ROI ORDER that has no packet, with
+ *     ICER_BYTE_QUOTA_EXCEEDED.  (So the byte-quota and cuts calls, which walk in priority order, cut a stored ROI stream
+ *     at the first background unit it lacks; this call, given the rectangle and shift it was made with, does not.)
+ *   - the frame statuses are icerx_recut_device_cuts_async's (ICER_DECODER_OUT_OF_DATA, ICER_INVALID_INPUT, no valid packet
+ *     above level r); size, K and the foreground count of such a frame are 0.
+ *   - every output is a subset of M_r's packets with both CRCs valid and no bit plane kept below a dropped one of its
+ *     family, so any decoder told stages - r decodes it.
+ * Arguments: the masters, d_out / out_stride / d_sizes / d_rcs (row and entry c * n + f) and the nothing-written promises
+ * are those of icerx_recut_device_cuts_async.  d_rois is DEVICE memory, n x 4 uint32 (x, y, w, h), read on `stream` -- a
+ * kernel that wrote it on the same stream just before needs no synchronisation -- per frame and shared by all cuts; values
+ * are read as uint32, so int32 values below 0 read as far outside.  `reduces`, `shifts` and `quotas` are HOST arrays of n_cuts
+ * entries passed by value; reduces == NULL means every reduce is 0 (any recutter serves such a call), otherwise each lies in
+ * 0 .. max_reduce; 0 <= shifts[c] <= ICERX_MAX_ROI_SHIFT, per cut, so one call delivers a plain cut and a ROI cut side by
+ * side.  d_kept / d_foreground: n_cuts * n entries each, K and the number of foreground units of the cut's geometry.
+ * The whole call returns ICER_INVALID_INPUT -- nothing enqueued, nothing written -- for what
+ * icerx_recut_device_cuts_async refuses (a null `reduces` excepted), a null d_rois, shifts, d_kept or d_foreground, a shift
+ * out of range, or a workspace below icerx_recut_roi_workspace_bytes(r, n, data_bytes, n_cuts) (the cuts call's, and 20 more
+ * bytes per frame, cut and coding unit of the full geometry).  Stream-ordered with every promise of the calls above: no
+ * blocking copy, no synchronisation, no hipMalloc / hipFree, no host round trip.  Every recutter holds, from its creation,
+ * the priority of every unit's packet for every geometry 0 .. max_reduce (8 bytes per unit); a geometry whose priorities do
+ * not fit the sort keys makes the create call return ICER_FATAL_ERROR (no geometry the planner accepts does). */
+size_t icerx_recut_roi_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts);
+int icerx_recut_device_roi_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                 size_t stream_stride, const uint64_t *d_lens, const uint32_t *d_rois, const int *reduces,
+                                 const int *shifts, const size_t *quotas, int n_cuts, uint8_t *d_out, size_t out_stride,
+                                 uint64_t *d_sizes, int32_t *d_rcs, uint32_t *d_kept, uint32_t *d_foreground,
+                                 void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* last error message of this thread's most recent failing call ("" if none) */
 const char *icerx_decoder_last_error(void);
 
