@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from icer_compression_amd import api, synth
+from tests.test_gpu_ladder import device_frames
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,7 +48,7 @@ def test_forced_timeout_is_reported_counted_and_recoded(oracle, capfd, use_async
     quota = 2 * w * h
     frames = synth.gray_batch(n, w, h, 505, 1)
     want = [oracle.compress([frames[k]], st, 0, sg, quota) for k in range(n)]
-    d_frames = torch.from_numpy(frames.view(np.int16)).to(dev)
+    d_frames = device_frames(frames)
     out = torch.zeros((n, quota), dtype=torch.uint8, device=dev)
     sizes = torch.zeros(n, dtype=torch.int64, device=dev)
     rcs = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -82,7 +83,7 @@ def test_forced_timeout_in_a_split_unit_of_a_lone_frame(oracle, capfd):
     quota = 2 * w * h
     frame = synth.gray_frame(w, h, 606, 1)
     want = oracle.compress([frame], st, 0, sg, quota)
-    d_frames = torch.from_numpy(frame.view(np.int16)[None]).to(dev)
+    d_frames = device_frames(frame[None])
     out = torch.zeros((1, quota), dtype=torch.uint8, device=dev)
     sizes = torch.zeros(1, dtype=torch.int64, device=dev)
     rcs = torch.zeros(1, dtype=torch.int32, device=dev)
