@@ -309,6 +309,9 @@ int icerx_recut_device_cuts_async(icerx_recutter *r, int n, const void *d_data, 
  *     are that geometry's own, and the headers are relabelled as in icerx_recut_device_cuts_async.
  *     Since floor((x0 >> r) / 2^l) = floor(x0 / 2^(l + r)), and the same for the ceilings, a non-LL unit of level l at
  *     1/2^r size is foreground exactly when the master's unit of level l + r is; only LL and the priorities differ.
+ *     (Where the planner keeps a grid -- a subband with fewer samples than segments takes the rectangles of the packet
+ *     before it, and which packet that is depends on the priorities -- the rectangles of the plan at 1/2^r size, not the
+ *     ones the master's payloads were coded with, decide foreground.)
  * Consequences:
  *   - r = 0 and a complete master: bytes, size, return code, K and the foreground count of icerx_encode_device_roi on the
  *     original frame with the same rectangle, shift and quota.

@@ -1,6 +1,10 @@
 """A seeded sample of frame geometries for the rate ladder, the re-cut and the quality target (icerx_encode_device_ladder,
 icerx_recut_device_async, icerx_encode_device_target), shared by tests/test_geometry_sweep.py (CPU) and
-tests/test_gpu_geometry_sweep.py.
+tests/test_gpu_geometry_sweep.py.  The same sample, with a rectangle per frame and a list of (reduce, quota, shift) cuts
+(tests/sweep_cut_cases.py), runs through the ROI encode, the re-cuts by resolution and by region, the reduced decoders and the
+display decode (icerx_encode_device_roi, icerx_recut_device_cuts_async, icerx_recut_device_roi_async,
+icerx_decoder_create_reduced): tests/test_geometry_sweep_cuts.py (CPU) and tests/test_gpu_geometry_sweep_cuts.py; and
+tests/test_emu_roi.py and tests/test_gpu_budget_sweep.py take their geometries from it.
 
 Draws: sides 9 .. 200 with at most 40 000 samples a frame, 1 .. 6 stages, filters 0 .. 6, 1 .. 32 segments, 1 or 3 channels,
 16 or 8 bits, and a batch of three frame specs.  A draw is kept only if the oracle codes every frame of its batch at the

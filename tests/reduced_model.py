@@ -1,7 +1,9 @@
 """The definition of the reduced-resolution decode (include/icer_hip_dec.h, "Decoding at 1/2^r resolution") in plain Python:
 derive(X, r) builds the derived stream X_r of a stream X, and the reduced decode of X at r IS the plain decode of X_r at
 stages - r.  Shared by tests/test_reduced_model.py, test_reduced_plan_device.py, test_reduced_mock.py and test_gpu_reduced.py;
-also the specification of a future recutter that cuts by resolution.  zlib.crc32 is the reference's CRC."""
+also the specification of the recutter's cuts by resolution.  zlib.crc32 is the reference's CRC.  (One exception, stated in the
+header: a chain whose packets do not decode within their own payloads reads on into the bytes that follow in X, which are not
+the ones that follow in X_r; tests/sweep_cut_cases.reads_on finds such streams with the decoder oracle.)"""
 import zlib
 
 import numpy as np

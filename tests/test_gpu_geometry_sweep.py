@@ -3,7 +3,8 @@ filters, 1 to 32 segments, gray and YUV, 16 and 8 bits, grids kept under quirk P
 several thousand units -- one encoder runs the rate ladder against the oracle, re-cuts its own lossless masters to the same
 quotas against the oracle, makes the quality-targeted encode under two byte caps against the plain model (energy table, D[K],
 the cut rule, the separate call at the equivalent quota), and feeds one re-cut quota block to the decoder beside the oracle's
-streams.  Every comparison is exact.  The CPU side of the same sample is tests/test_geometry_sweep.py."""
+streams, both compared with the decoder oracle.  Every comparison is exact.  The CPU side of the same sample is
+tests/test_geometry_sweep.py."""
 import numpy as np
 import pytest
 
@@ -94,9 +95,13 @@ def test_ladder_recut_target_and_chain(torch, oracle, expected, case):          
         assert rc == 0
         for f in range(n):
             assert (int(rcs[f]), int(ws[f]), int(hs[f])) == want[f][:3], (what, f, int(rcs[f]), want[f][:3])
+            # both against the decoder oracle on the oracle's stream (a kept grid of quirk P1 ends it with rc -3, the words stay)
+            orc = oracle.decompress(expected(g, specs[f], quota)[1], g.channels, g.stages, g.filt, g.segments, bufsize=g.w * g.h, bits=g.bits)
+            assert want[f][:3] == orc[:3] == (-3 if gsc.is_p1(g) else 0, g.w, g.h), (what, f, want[f][:3], orc[:3])
             for c in range(g.channels):
                 p = planes[f, c].cpu().numpy()
                 assert np.array_equal(p.view(np.uint16) if g.bits == 16 else p, want[f][3][c]), (what, f, c)
+                assert np.array_equal(want[f][3][c], orc[3][c]), (what, f, c, "decode_host differs from the decoder oracle")
     finally:
         d.close()
     assert enc.stats()["unit_timeouts"] == 0
