@@ -2,8 +2,8 @@
 // a BATCH of streams (the lib_icer-shaped entry points are batches of one):
 //   streams -> device | header candidates (one thread per byte offset, grid.y = stream) | payload CRCs (one thread per
 //   candidate) | host: per stream the packet walk, table and chains (decoder_plan.hpp) | decode kernel over the
-//   chains of all streams (one wavefront per chain; one thread per chain with ICER_DEC_WAVE=0) | sign-magnitude
-//   removal + LL mean | inverse DWT, one level at a time, one thread per line, all frames of a geometry per launch
+//   chains of all streams (one wavefront per chain; one thread per chain with ICER_DEC_WAVE=0) | if the decoder asks
+//   for it, truncated coefficients part-way into their interval (decoder_recon.hpp) | sign-magnitude removal + LL mean | inverse DWT, one level at a time, one thread per line, all frames of a geometry per launch
 //   | clamp, narrow, copy back.
 // icerx_decode_device_async runs the same chain kernels with everything planned on the device (decoder_async.hpp).
 // First version: correctness before speed (HISTORY.md 6b (summary: DESIGN.md 8)); every loop is bounded by the stream / image size and no
@@ -258,6 +258,7 @@ finish_kernel(uint16_t *__restrict__ planes, size_t frame_stride, int channels, 
 }  // namespace
 
 #include "decoder_display.hpp"         // display_finish_kernel: the last pass of the *_display calls, in finish_kernel's place
+#include "decoder_recon.hpp"           // reconstruct_kernel: truncated coefficients part-way into their interval, before unsign_kernel
 
 // ------------------------------------------------------------------------------------------ decoder object
 // The side streams carry the kernels of the ring size classes side by side with the plane kernel on the call's own stream.  The HIP runtime
@@ -287,6 +288,9 @@ struct icerx_decoder {
     // a reduced-resolution decoder (icerx_decoder_create_reduced): made for streams of stages + reduce stages, it decodes their
     // derived streams (plan_decode) -- `stages` is what is left to run, and everything below the planners goes by it alone
     int reduce = 0;
+    // icerx_decoder_set_reconstruction: eighths of the interval a truncated non-zero coefficient is rebuilt at (0: its low end,
+    // the reference's decode); read once when a call is enqueued
+    int recon = 0;
     unsigned segments = 1;
     DecoderTables tables;
     uint32_t crc_tab[256];
@@ -387,6 +391,7 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
     int rc = ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits, stages = d->stages;
     const int nplanes = bits == 8 ? kPlanes8 : kPlanes, sign_bit = bits == 8 ? 7 : 15;
+    const int recon = d->recon;
     size_t total_len = 0, max_len = 0;
     for (int k = 0; k < n; k++) {
         if (lens[k] && !data) return ICER_INVALID_INPUT;
@@ -597,6 +602,11 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
     // 4. samples
     {
         const dim3 grid_all((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * channels));
+        if (recon != 0 && !chains.empty()) {                 // (the chain kernels are complete: the side streams were waited for)
+            ICER_LAUNCH(reconstruct_kernel, dim3((unsigned)chains.size(), kReconParts), kReconThreads, 0, d_planes, frame_stride, channels,
+                        (const ChainDesc *)d->chains.p, (uint32_t)chains.size(), d_frames, (uint32_t)n, nplanes, sign_bit, recon);
+            HIP_TRY(hipGetLastError());
+        }
         ICER_LAUNCH(unsign_kernel, grid_all, 256, 0, d_planes, frame_stride, channels, d_frames, sign_bit, bits);
         HIP_TRY(hipGetLastError());
         // inverse DWT: the frames of one size together
@@ -688,14 +698,16 @@ done:
 }
 
 int decompress_planes(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
-                      const uint8_t *data, size_t data_length, int stages, int filt, unsigned segments, int bits, int reduce = 0)
+                      const uint8_t *data, size_t data_length, int stages, int filt, unsigned segments, int bits, int reduce = 0,
+                      int eighths = 0)
 {
-    if (!image_w || !image_h || (!data && data_length)) return ICER_INVALID_INPUT;
+    if (!image_w || !image_h || (!data && data_length) || eighths < 0 || eighths > kReconMax) return ICER_INVALID_INPUT;
     for (int c = 0; c < channels; c++)
         if (!planes[c]) return ICER_INVALID_INPUT;
     icerx_decoder *d = nullptr;
     int rc = icerx_decoder_create_reduced(&d, -1, channels, stages, filt, segments, bits, reduce);
     if (rc != ICER_RESULT_OK) return rc;
+    d->recon = eighths;
     const size_t off = 0;
     int frame_rc = ICER_RESULT_OK;
     rc = decode_batch(d, 1, data, false, &off, &data_length, planes, nullptr, bufsize, &frame_rc, image_w, image_h);
@@ -720,6 +732,15 @@ int icerx_decoder_create(icerx_decoder **out, int device, int channels, int stag
 }
 
 int icerx_decoder_reduce(const icerx_decoder *dec) { return dec ? dec->reduce : 0; }
+
+int icerx_decoder_set_reconstruction(icerx_decoder *dec, int eighths)
+{
+    if (!dec || eighths < 0 || eighths > kReconMax) return ICER_INVALID_INPUT;
+    dec->recon = eighths;
+    return ICER_RESULT_OK;
+}
+
+int icerx_decoder_reconstruction(const icerx_decoder *dec) { return dec ? dec->recon : 0; }
 
 void icerx_reduced_size(size_t w, size_t h, int reduce, size_t *rw, size_t *rh)
 {
@@ -909,6 +930,15 @@ int icerx_decompress_reduced(void *const planes[], int channels, size_t *image_w
     if (!planes || (channels != 1 && channels != 3)) return ICER_INVALID_INPUT;
     return decompress_planes(planes, channels, image_w, image_h, bufsize, datastream, data_length, stages, (int)filt, segments,
                              sample_bits, reduce);
+}
+
+int icerx_decompress_reconstructed(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
+                                   const uint8_t *datastream, size_t data_length, int stages, int filt, unsigned segments,
+                                   int sample_bits, int reduce, int eighths)
+{
+    if (!planes || (channels != 1 && channels != 3)) return ICER_INVALID_INPUT;
+    return decompress_planes(planes, channels, image_w, image_h, bufsize, datastream, data_length, stages, filt, segments,
+                             sample_bits, reduce, eighths);
 }
 
 int icer_decompress_image_uint16(uint16_t *image, size_t *image_w, size_t *image_h, size_t image_bufsize,

@@ -11,7 +11,7 @@
 //              the device, then each chain placed in its kernel's list, largest area first
 //   chains     persistent list-driven wrappers of the three chain kernels: wave per plane on the caller's stream, the lane-per-
 //              plane ring classes on the decoder's side streams (forked and joined with events), thread per chain
-//   samples    unsign_kernel, the inverse DWT with each frame's own size (the level loop on the host runs over `stages`),
+//   samples    reconstruct_kernel if the decoder asks for it (decoder_recon.hpp), unsign_kernel, the inverse DWT with each frame's own size (the level loop on the host runs over `stages`),
 //              finish_kernel; a wave-per-plane chain past its spin bound turns its frame's rc into ICER_FATAL_ERROR
 // The blob stage and the walk are also the first two steps of a re-cut (recut.hpp), which has no copy of either.
 #include "decoder_dplan.hpp"
@@ -559,6 +559,7 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     int rc = ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits, stages = d->stages;
     const int nplanes = bits == 8 ? kPlanes8 : kPlanes, sign_bit = bits == 8 ? 7 : 15;
+    const int recon = d->recon;
     const DPlanGeom geom = async_geom(d);
     uint8_t *ws = (uint8_t *)workspace;
     AsyncHead *head = (AsyncHead *)(ws + L.blob.head);
@@ -670,6 +671,11 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     // 4. samples
     {
         const dim3 grid_all((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * channels));
+        if (recon != 0 && slots) {                           // (behind the joins: every chain kernel is complete)
+            ICER_LAUNCH_ON(st, reconstruct_kernel, dim3(slots, kReconParts), kReconThreads, 0, planes, frame_stride, channels,
+                           (const ChainDesc *)chains, slots, (const FrameInfo *)frames, (uint32_t)n, nplanes, sign_bit, recon);
+            HIP_TRY(hipGetLastError());
+        }
         ICER_LAUNCH_ON(st, unsign_kernel, grid_all, 256, 0, planes, frame_stride, channels, frames, sign_bit, bits);
         HIP_TRY(hipGetLastError());
         const FilterTaps taps = filter_taps(d->filt);

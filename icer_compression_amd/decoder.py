@@ -57,6 +57,12 @@ def bind(path: str) -> C.CDLL:
         lib.icerx_reduced_size.argtypes = [_sz, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz)]
         lib.icerx_reduced_size.restype = None
         lib.icerx_decompress_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int] + tail + [C.c_int, C.c_int]
+    # truncated coefficients rebuilt inside their interval
+    if hasattr(lib, "icerx_decoder_set_reconstruction"):
+        lib.icerx_decoder_set_reconstruction.argtypes = [C.c_void_p, C.c_int]
+        lib.icerx_decoder_reconstruction.argtypes = [C.c_void_p]
+        lib.icerx_decompress_reconstructed.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(_sz), C.POINTER(_sz), _sz, _u8p, _sz,
+                                                       C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]
     # re-cutting by resolution as well as by byte quota
     if hasattr(lib, "icerx_recut_device_cuts_async"):
         lib.icerx_recutter_create_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int, _sz, _sz, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
@@ -107,9 +113,11 @@ def reduced_size(w: int, h: int, r: int):
 
 
 def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: int, bufsize: int | None = None, bits: int = 16,
-               lib=None, reduce: int = 0):
+               lib=None, reduce: int = 0, reconstruct: int = 0):
     """icer_decompress_image_[yuv_]uint16 / _uint8 on a host stream -> (rc, w, h, [flat planes of bufsize samples]).
-    reduce = r > 0: icerx_decompress_reduced, the image at 1/2^r size; bufsize then counts samples of the reduced image."""
+    reduce = r > 0: icerx_decompress_reduced, the image at 1/2^r size; bufsize then counts samples of the reduced image.
+    reconstruct = k in 1..4: icerx_decompress_reconstructed, truncated non-zero coefficients rebuilt k eighths of the way into
+    their interval (3 is the recommended value; 0 is the reference's decode)."""
     lib = lib or load_library()
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
@@ -120,6 +128,12 @@ def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: i
         bufsize = w * h if rc == 0 else 0
     buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
     planes = [np.zeros(max(bufsize, 1), np.uint16 if bits == 16 else np.uint8) for _ in range(channels)]
+    if reconstruct != 0:
+        fn = _need(lib, "icerx_decompress_reconstructed")
+        ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
+        w, h = _sz(0), _sz(0)
+        rc = fn(ptrs, channels, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, bits, reduce, reconstruct)
+        return rc, w.value, h.value, planes
     if reduce != 0:
         fn = _need(lib, "icerx_decompress_reduced")
         ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
@@ -132,13 +146,28 @@ def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: i
     return rc, w.value, h.value, planes
 
 
-def decompress_display(stream: bytes, channels: int, stages: int, filt: int, segments: int, lib=None):
+def decompress_display(stream: bytes, channels: int, stages: int, filt: int, segments: int, lib=None, reconstruct: int = 0):
     """icerx_decompress_display on a host 16-bit stream -> (rc, image): uint8 (h, w) for channels 1 (gray8), (h, w, 3) for
-    channels 3 (RGB888), the image the reference's `icer_util decompress` writes; an empty array when nothing was decoded."""
+    channels 3 (RGB888), the image the reference's `icer_util decompress` writes; an empty array when nothing was decoded.
+    reconstruct = k in 1..4: through a Decoder with that setting (icerx_decode_host_display)."""
     lib = lib or load_library()
     fn = _need(lib, "icerx_decompress_display")
     rc0, w0, h0 = icer_get_image_dimensions(stream, lib)
     bufsize = w0 * h0 if rc0 == 0 else 0
+    if reconstruct != 0:
+        if channels not in (1, 3):
+            return -11, np.zeros((0, 0), np.uint8)
+        dec = Decoder(channels, stages, filt, segments, lib=lib, reconstruct=reconstruct)
+        try:
+            rc, res = dec.decode_display_host([stream], bufsize)
+        finally:
+            dec.close()
+        rc_k, w_k, h_k, row = res[0]
+        rc = rc if rc != 0 else rc_k
+        if w_k * h_k == 0 or w_k * h_k > bufsize:
+            return rc, np.zeros((0, 0) if channels != 3 else (0, 0, 3), np.uint8)
+        row = row[: channels * w_k * h_k]
+        return rc, row.reshape((h_k, w_k) if channels == 1 else (h_k, w_k, 3))
     buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
     image = np.zeros(max(bufsize * max(channels, 1), 1), np.uint8)
     w, h = _sz(0), _sz(0)
@@ -176,9 +205,11 @@ class Decoder:
     """Batch / device-resident extension (icerx_decoder_*, include/icer_hip_dec.h Part 2)."""
 
     def __init__(self, channels: int, stages: int, filt: int, segments: int, bits: int = 16, device: int = -1, lib=None,
-                 reduce: int = 0):
+                 reduce: int = 0, reconstruct: int = 0):
         """reduce = r > 0: a decoder for streams made with `stages` that delivers every image at 1/2^r size
-        (icerx_decoder_create_reduced): strides and buffer sizes count samples of the reduced image, ws / hs report its size"""
+        (icerx_decoder_create_reduced): strides and buffer sizes count samples of the reduced image, ws / hs report its size.
+        reconstruct = k in 1..4: truncated non-zero coefficients are rebuilt k eighths of the way into their interval in every
+        call of this decoder (icerx_decoder_set_reconstruction; 3 is the recommended value, 0 the reference's decode)"""
         self.lib = lib or load_library()
         self.channels, self.bits, self.reduce = channels, bits, 0
         self.lib.icerx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int]
@@ -204,10 +235,28 @@ class Decoder:
             if rc != 0:
                 raise RuntimeError(f"icerx_decoder_create_reduced: {rc} {self.lib.icerx_decoder_last_error().decode()}")
             self.reduce = int(self.lib.icerx_decoder_reduce(self.handle))
-            return
-        rc = self.lib.icerx_decoder_create(C.byref(self.handle), device, channels, stages, filt, segments, bits)
+        else:
+            rc = self.lib.icerx_decoder_create(C.byref(self.handle), device, channels, stages, filt, segments, bits)
+            if rc != 0:
+                raise RuntimeError(f"icerx_decoder_create: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+        if reconstruct != 0:
+            self.set_reconstruction(reconstruct)
+
+    @property
+    def reconstruct(self) -> int:
+        """the decoder's reconstruction point in eighths (icerx_decoder_reconstruction; 0 on a build without it)"""
+        if not hasattr(self.lib, "icerx_decoder_reconstruction"):
+            return 0
+        self.lib.icerx_decoder_reconstruction.argtypes = [C.c_void_p]
+        return int(self.lib.icerx_decoder_reconstruction(self.handle))
+
+    def set_reconstruction(self, eighths: int) -> None:
+        """icerx_decoder_set_reconstruction: 0..4, for every call enqueued from now on"""
+        fn = _need(self.lib, "icerx_decoder_set_reconstruction")
+        fn.argtypes = [C.c_void_p, C.c_int]
+        rc = fn(self.handle, eighths)
         if rc != 0:
-            raise RuntimeError(f"icerx_decoder_create: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+            raise ValueError(f"icerx_decoder_set_reconstruction({eighths}): {rc}")
 
     def close(self):
         if self.handle:

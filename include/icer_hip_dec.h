@@ -184,6 +184,34 @@ int icerx_decompress_reduced(void *const planes[], int channels, size_t *image_w
                              const uint8_t *datastream, size_t data_length, uint8_t stages, enum icer_filter_types filt,
                              uint8_t segments, int sample_bits, int reduce);
 
+/* ---- Reconstructing truncated coefficients inside their interval ------------------------------------------------------
+ * Every lossy stream of this library is a truncated bit-plane stream.  A coefficient whose lowest p planes never arrived is
+ * known to lie in [m, m + 2^p - 1]; lib_icer, and this decoder by default, rebuild it at m.  A decoder can be told to rebuild
+ * every NON-ZERO coefficient k eighths of the way into that interval instead.  It costs no stream bytes and changes no
+ * stream.  The rule is exact and in integers:
+ *     P = 9 coded planes (16-bit decoder) or 7 (8-bit).  For a chain (channel, level, subband, segment): t = the packets
+ *     present consecutively from plane P - 1 downwards (the planes the chain runs), p = P - t -- the planner's figure: a
+ *     packet whose decode stops early inside still counts.  off(p, k) = (k * (2^p - 1)) >> 3.
+ *     After the entropy stage and before sign-magnitude removal, every word of the chain's rectangle with a non-zero
+ *     magnitude becomes magnitude + off(p, k); the sign stays, a zero magnitude stays (with or without a set sign bit).  LL
+ *     chains as well.  Only frames that reach the transform: a frame that stops early keeps its words as they are.
+ * Everything behind that step is as before: the LL mean, the inverse transform, the clamp, narrowing, display conversion,
+ * return codes.  k = 0 is the plain decoder byte for byte, and a lossless stream (p = 0 everywhere) decodes identically for
+ * every k.  For a reduced decoder the rule applies to the chains of the derived stream.
+ * k = 3 is the recommended value: it lowered the squared error in every case measured (profiles/decode_recon.md; about
+ * 0.6 dB at medium rates), while the midpoint k = 4 is sometimes worse than k = 0. */
+
+/* eighths in 0 .. 4, anything else: ICER_INVALID_INPUT and the decoder stays as it was.  The setting holds for every entry
+ * point that takes the decoder (host, device, async, the three display calls; reduced decoders too) and is read when a call
+ * is enqueued: asynchronous calls already in flight keep theirs.  The lib_icer drop-in calls icer_decompress_image_* stay
+ * at the reference's reconstruction. */
+int icerx_decoder_set_reconstruction(icerx_decoder *dec, int eighths);
+int icerx_decoder_reconstruction(const icerx_decoder *dec);                        /* the decoder's setting (0 for NULL) */
+/* the one-shot call, shaped like icerx_decompress_reduced (reduce 0: full size) */
+int icerx_decompress_reconstructed(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
+                                   const uint8_t *datastream, size_t data_length, int stages, int filt, unsigned segments,
+                                   int sample_bits, int reduce, int eighths);
+
 /* ---- Re-cutting stored streams to smaller byte quotas ---------------------------------------------------------------
  * A byte quota decides only where a stream is cut, never what a packet holds.  So from a stored master stream M of a frame
  * -- made by this project's encoders or by the reference at quota Qm, return code ICER_RESULT_OK or
