@@ -79,6 +79,13 @@ def bind(path: str) -> C.CDLL:
         lib.icerx_recut_device_roi_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p,
                                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz), C.c_int, C.c_void_p, _sz,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
+    # refinement increments: the difference and the union of two stored streams
+    if hasattr(lib, "icerx_combine_device_async"):
+        lib.icerx_combine_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz]
+        lib.icerx_combine_workspace_bytes.restype = _sz
+        lib.icerx_combine_device_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p,
+                                                   _sz, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   _sz, C.c_void_p]
     return lib
 
 
@@ -420,6 +427,7 @@ class Decoder:
 
 
 MAX_LADDER = 16                  # ICERX_MAX_LADDER
+COMBINE_UNION, COMBINE_DIFFERENCE = 0, 1         # ICERX_COMBINE_UNION / ICERX_COMBINE_DIFFERENCE
 
 
 class Recutter:
@@ -449,6 +457,7 @@ class Recutter:
         self._workspaces = {}                # recut_torch: one cached workspace per torch stream
         self._cuts_workspaces = {}           # recut_cuts_torch: the same, sized for the cuts call
         self._roi_workspaces = {}            # recut_roi_torch: the same, sized for the ROI call
+        self._combine_workspaces = {}        # combine_torch: the same, sized for the combine call
         self.handle = C.c_void_p()
         self.max_reduce = 0
         if max_reduce != 0:
@@ -469,6 +478,7 @@ class Recutter:
         self._workspaces.clear()
         self._cuts_workspaces.clear()
         self._roi_workspaces.clear()
+        self._combine_workspaces.clear()
 
     def __del__(self):
         try:
@@ -673,6 +683,92 @@ class Recutter:
                                               work.numel(), st.cuda_stream)
         if rc != 0:
             raise RuntimeError(f"icerx_recut_device_roi_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+
+
+    # ---- refinement increments: the difference and the union of two stored streams (icerx_combine_device_async) ----
+    def combine_workspace_bytes(self, n: int, data_bytes: int) -> int:
+        """icerx_combine_workspace_bytes: the device workspace one combine_device_async_ptrs call needs"""
+        return int(_need(self.lib, "icerx_combine_workspace_bytes")(self.handle, n, data_bytes))
+
+    def combine_device_async_ptrs(self, n: int, op: int, d_data: int, data_bytes: int, d_offsets_a, base_a: int, d_lens_a: int, d_offsets_b,
+                                  base_b: int, d_lens_b: int, stream_stride: int, d_out: int, out_stride: int, d_sizes: int, d_rcs: int,
+                                  d_counts: int, d_workspace: int, workspace_bytes: int, stream: int = 0) -> int:
+        """icerx_combine_device_async on raw device pointers.  Both operands lie in the blob d_data: frame k of operand X is
+        [off, off + lens_x[k]) with off = offsets_x[k], or base_x + k * stream_stride when d_offsets_x is None (offsets, lens,
+        sizes: uint64 / int64; rcs: int32; counts: uint32, entries 2 k and 2 k + 1 = packets written, of them from A).  Frame k
+        is row k of d_out.  Enqueues on `stream` and returns the call's rc without waiting."""
+        fn = _need(self.lib, "icerx_combine_device_async")
+        return fn(self.handle, n, op, d_data, data_bytes, d_offsets_a, base_a, d_lens_a, d_offsets_b, base_b, d_lens_b, stream_stride, d_out,
+                  out_stride, d_sizes, d_rcs, d_counts, d_workspace, workspace_bytes, stream)
+
+    def combine_torch(self, data, op, lens_a, lens_b, out, sizes, rcs, counts, offsets_a=None, offsets_b=None, base_a=0, base_b=0,
+                      stream_stride=None) -> None:
+        """The union (COMBINE_UNION) or the difference (COMBINE_DIFFERENCE: the packets of B that A lacks) of two stored streams
+        per frame, on torch's current stream, without waiting.
+
+        data: one cuda uint8 tensor that holds both operands, of any shape; lens_a / lens_b (and offsets_a / offsets_b, if given):
+        cuda int64 (n,).  Without offsets frame k of operand X starts at base_x + k * stream_stride bytes (default:
+        data.stride(-2) of a blob with rows), so the output of one recut_*_torch call with the held cut c and the wanted cut d
+        goes in as it is: data = out, base_a = c * n * out_stride, base_b = d * n * out_stride, lens sizes[c] and sizes[d].
+        out: cuda uint8 (n, out_stride); sizes: cuda int64 (n,); rcs: cuda int32 (n,); counts: cuda int32 (n, 2) or 2 n entries.
+        A frame whose result is longer than out_stride gets ICER_OUTPUT_BUF_TOO_SMALL, the bytes needed in sizes and an untouched
+        row.  The workspace is cached per stream, apart from the other calls'."""
+        import torch
+        n = int(lens_a.shape[0])
+        if stream_stride is None:
+            if offsets_a is None or offsets_b is None:
+                if data.dim() < 2:
+                    raise ValueError("a 1-D blob needs offsets or stream_stride")
+                stream_stride = data.stride(-2)
+            else:
+                stream_stride = 0
+        for name, t, dt in (("data", data, torch.uint8), ("lens_a", lens_a, torch.int64), ("lens_b", lens_b, torch.int64),
+                            ("out", out, torch.uint8), ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32),
+                            ("counts", counts, torch.int32)) + \
+                tuple((nm, t, torch.int64) for nm, t in (("offsets_a", offsets_a), ("offsets_b", offsets_b)) if t is not None):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
+                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        if out.dim() != 2 or out.shape[0] != n or any(t.numel() != n for t in (lens_b, sizes, rcs)) or counts.numel() != 2 * n or \
+                any(t is not None and t.numel() != n for t in (offsets_a, offsets_b)):
+            raise ValueError("out must be (n, out_stride), lens, offsets, sizes and rcs n entries, counts 2 n")
+        st = torch.cuda.current_stream(data.device)
+        need = self.combine_workspace_bytes(n, data.numel())
+        work = self._combine_workspaces.get(st.cuda_stream)
+        if work is None or work.numel() < max(need, 1):
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
+            self._combine_workspaces[st.cuda_stream] = work
+        work.record_stream(st)
+        rc = self.combine_device_async_ptrs(n, op, data.data_ptr(), data.numel(), offsets_a.data_ptr() if offsets_a is not None else None,
+                                            int(base_a), lens_a.data_ptr(), offsets_b.data_ptr() if offsets_b is not None else None,
+                                            int(base_b), lens_b.data_ptr(), int(stream_stride), out.data_ptr(), out.shape[-1],
+                                            sizes.data_ptr(), rcs.data_ptr(), counts.data_ptr(), work.data_ptr(), work.numel(),
+                                            st.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"icerx_combine_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+
+    def combine(self, streams_a, streams_b, op):
+        """bytes in, bytes out: res[f] = (rc, stream, packets written, of them from A) of streams_a[f] and streams_b[f] under `op`
+        (copies to the device and back, and waits: a convenience, not the fast path)"""
+        import torch
+        if len(streams_a) != len(streams_b):
+            raise ValueError("one stream of each operand per frame")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n = len(streams_a)
+        both = list(streams_a) + list(streams_b)
+        lens = [len(s) for s in both]
+        blob = np.frombuffer(b"".join(both), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+        offs = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)).to(dev)
+        lens = torch.tensor(lens, dtype=torch.int64, device=dev)
+        stride = max(max(len(a) + len(b) for a, b in zip(streams_a, streams_b)), 1)
+        out = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
+        sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+        rcs = torch.zeros(n, dtype=torch.int32, device=dev)
+        counts = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        self.combine_torch(torch.from_numpy(blob).to(dev), op, lens[:n].contiguous(), lens[n:].contiguous(), out, sizes, rcs, counts,
+                           offsets_a=offs[:n].contiguous(), offsets_b=offs[n:].contiguous())
+        torch.cuda.current_stream(dev).synchronize()
+        out, sizes, rcs, counts = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy(), counts.cpu().numpy()
+        return [(int(rcs[f]), out[f, : int(sizes[f])].tobytes(), int(counts[f, 0]), int(counts[f, 1])) for f in range(n)]
 
 
 # ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------

@@ -376,6 +376,47 @@ int icerx_recut_device_roi_async(icerx_recutter *r, int n, const void *d_data, s
                                  uint64_t *d_sizes, int32_t *d_rcs, uint32_t *d_kept, uint32_t *d_foreground,
                                  void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Refinement increments: the difference and the union of two stored streams ------------------------------------------
+ * A decoder files every CRC-valid packet by (channel, level, subband, bit plane, segment) and does not mind the order of the
+ * packets, so a stream followed by the packets it lacks decodes exactly as the larger stream does.  This call computes those
+ * packets -- what to send to a client that holds cut A and wants cut B -- and the canonical stream of both.
+ * Operands: both live in one blob d_data[0, data_bytes).  Frame k of operand X is [off, off + d_lens_x[k]) with
+ * off = d_offsets_x[k], or base_x + k * stream_stride when d_offsets_x is NULL; the output block of a two-cut re-cut call plugs
+ * in as it is (base_a = 0, base_b = n * out_stride, lens d_sizes and d_sizes + n).  A zero-length operand is an empty set.  An
+ * operand may be any concatenation of streams and increments of one frame: it is walked with the decoder's cursor rule, as
+ * icerx_recut_device_async walks a master, so within an operand the last valid packet of a kind wins.  `r` is a recutter made
+ * for the streams' own geometry (for cuts at 1/2^r size: a plain recutter of the geometry at that size); only its tables of
+ * reduce 0 are used, and a packet that is not a coding unit of that plan is dropped.  Per unit u of the plan:
+ *   ICERX_COMBINE_UNION        kept when A or B has a valid packet of u; B's packet if B has one, else A's
+ *   ICERX_COMBINE_DIFFERENCE   kept when B has a valid packet of u and A has none; B's packet
+ * The kept packets are copied verbatim, header and payload, in the plan's final order.  "A has it" is decided by the unit
+ * alone, never by comparing payloads; a packet of A that fails a CRC is absent, so the difference against a damaged copy
+ * re-sends exactly the damaged packets.  When A's units are a part of B's: union(A, difference(A, B)) is B byte for byte, and
+ * the difference is len(B) - len(A) bytes.
+ * Per frame k: d_sizes[k], d_rcs[k], d_counts[2 k] = packets written, d_counts[2 k + 1] = how many of them came from A.
+ *   an operand leaves [0, data_bytes), or either operand holds a
+ *   valid packet whose width / height are not the recutter's      ICER_INVALID_INPUT, size 0, counts 0
+ *   UNION: neither operand holds a valid packet;
+ *   DIFFERENCE: B holds none                                       ICER_DECODER_OUT_OF_DATA, size 0, counts 0
+ *   the result is longer than out_stride                           ICER_OUTPUT_BUF_TOO_SMALL, d_sizes = the bytes needed, counts
+ *                                                                  valid, the row untouched (len_a + len_b for UNION, len_b
+ *                                                                  for DIFFERENCE always suffice)
+ *   otherwise                                                      ICER_RESULT_OK, the length (an empty difference: 0)
+ * Stream-ordered with every promise of icerx_recut_device_async: the call only enqueues -- no blocking copy, no
+ * synchronisation, no hipMalloc / hipFree; nothing is written behind a stream in its row, beyond the n rows, n entries or 2 n
+ * counts, to the blob or outside the workspace.  The whole call returns ICER_INVALID_INPUT -- nothing enqueued, nothing
+ * written -- for a null pointer (the two offset arrays and `stream` excepted), n outside 1 .. 65535, an `op` other than the
+ * two, or a workspace below icerx_combine_workspace_bytes(r, n, data_bytes) (about 4 bytes per blob byte, two packet tables
+ * per frame and 16 bytes per frame and coding unit); ICER_FATAL_ERROR for data_bytes past the 32-bit limit, as in the re-cut. */
+#define ICERX_COMBINE_UNION      0
+#define ICERX_COMBINE_DIFFERENCE 1
+size_t icerx_combine_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes);
+int icerx_combine_device_async(icerx_recutter *r, int n, int op, const void *d_data, size_t data_bytes,
+                               const uint64_t *d_offsets_a, size_t base_a, const uint64_t *d_lens_a,
+                               const uint64_t *d_offsets_b, size_t base_b, const uint64_t *d_lens_b, size_t stream_stride,
+                               uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, uint32_t *d_counts,
+                               void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* last error message of this thread's most recent failing call ("" if none) */
 const char *icerx_decoder_last_error(void);
 
