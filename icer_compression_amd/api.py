@@ -20,6 +20,8 @@ import os
 
 import numpy as np
 
+from ._abi import ENCODER, c_array, declare, icer_output_data_buf_typedef  # noqa: F401  (the struct is part of this module's interface)
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 # (ICER_HIP_LIB: another build of the same library, e.g. one made with different tuning flags -- measurements only)
 LIB_PATH = os.environ.get("ICER_HIP_LIB") or os.path.join(PKG, "libicer_hip.so")
@@ -41,11 +43,6 @@ ICERX_NUM_STAGES = 4
 STAGE_NAMES = ("dwt", "ll_mean+sign_magnitude", "code_units", "scan+gather")
 
 
-class icer_output_data_buf_typedef(C.Structure):       # icer.h:307-312
-    _fields_ = [("size_used", C.c_size_t), ("size_allocated", C.c_size_t),
-                ("data_start", C.c_void_p), ("rearrange_start", C.c_void_p)]
-
-
 class IcerHipError(RuntimeError):
     pass
 
@@ -61,58 +58,8 @@ def load_library() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise IcerHipError(f"{LIB_PATH} is missing: build it with `python -m icer_compression_amd.build` "
                            "(hipcc, gfx950).  There is no CPU fallback.")
-    L = C.CDLL(LIB_PATH, mode=os.RTLD_LOCAL)
-    u16 = C.c_void_p
-    L.icer_init.restype = C.c_int
-    L.icer_init_output_struct.argtypes = [C.POINTER(icer_output_data_buf_typedef), C.c_void_p, C.c_size_t, C.c_size_t]
-    L.icer_compress_image_uint16.argtypes = [u16, C.c_size_t, C.c_size_t, C.c_uint8, C.c_int, C.c_uint8,
-                                             C.POINTER(icer_output_data_buf_typedef)]
-    L.icer_compress_image_yuv_uint16.argtypes = [u16, u16, u16, C.c_size_t, C.c_size_t, C.c_uint8, C.c_int, C.c_uint8,
-                                                 C.POINTER(icer_output_data_buf_typedef)]
-    L.icer_compress_image_uint8.argtypes = L.icer_compress_image_uint16.argtypes
-    L.icer_compress_image_yuv_uint8.argtypes = L.icer_compress_image_yuv_uint16.argtypes
-    L.icerx_encoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
-                                       C.c_int, C.c_int]
-    L.icerx_encoder_create_ex.argtypes = L.icerx_encoder_create.argtypes + [C.c_int]
-    L.icerx_encoder_destroy.argtypes = [C.c_void_p]
-    L.icerx_encoder_destroy.restype = None
-    L.icerx_encode_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
-                                      C.c_void_p, C.c_void_p]
-    L.icerx_encode_device_async.argtypes = L.icerx_encode_device.argtypes
-    L.icerx_encode_device_ladder.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]
-    L.icerx_encode_device_target.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.icerx_encode_device_budget.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_size_t, C.c_void_p, C.c_size_t,
-                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.icerx_encode_device_roi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.icerx_target_threshold.restype = C.c_uint64
-    L.icerx_target_threshold.argtypes = [C.c_void_p, C.c_double]
-    L.icerx_get_distortion_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.icerx_encoder_wait.argtypes = [C.c_void_p]
-    L.icerx_compress_batch_uint16.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t,
-                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
-    L.icerx_compress_batch_uint16_devices.argtypes = L.icerx_compress_batch_uint16.argtypes[:-1] + [C.POINTER(C.c_int), C.c_int]
-    L.icerx_batch_release.restype = None
-    L.icerx_encode_device_u8.argtypes = L.icerx_encode_device.argtypes
-    L.icerx_encode_device_rgb8.argtypes = L.icerx_encode_device.argtypes
-    L.icerx_encode_device_s8.argtypes = L.icerx_encode_device.argtypes
-    L.icerx_encode_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    L.icerx_get_coefficients.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.icerx_timing_enable.argtypes = [C.c_void_p, C.c_int]
-    L.icerx_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
-    L.icerx_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
-    L.icerx_encoder_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.icerx_encoder_routing.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    L.icerx_encoder_launch_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    L.icerx_encoder_parts.argtypes = [C.c_void_p]
-    L.icerx_process_stats.argtypes = [C.POINTER(C.c_uint64)]
-    L.icerx_pin_host.argtypes = [C.c_void_p, C.c_size_t]
-    L.icerx_unpin_host.argtypes = [C.c_void_p]
-    L.icerx_last_error.restype = C.c_char_p
-    _lib = L
-    return L
+    _lib = declare(C.CDLL(LIB_PATH, mode=os.RTLD_LOCAL), ENCODER)
+    return _lib
 
 
 # ---- lib_icer-shaped entry points --------------------------------------------------------------
@@ -195,6 +142,22 @@ def compress(planes, stages: int, filt: int, segments: int, byte_quota: int):
 
 
 # ---- batched / device-resident extension ----------------------------------------------------------
+def _check(name: str, rc: int, detail=None) -> None:
+    """rc -> IcerHipError; detail: the text behind the code, by default the library's last error"""
+    if rc != 0:
+        raise IcerHipError(f"{name} rc={rc}" + (": " + load_library().icerx_last_error().decode() if detail is None else detail))
+
+
+def _cut_outputs(frames, rows: int, stride: int, int64s: int = 1, int32s: int = 1):
+    """the outputs of a call that cuts every frame `rows` times, on the frames' device: the streams, uint8 (rows, n, stride), and
+    lists of int64 and of int32 tensors (rows, n)"""
+    import torch
+    n, dev = frames.shape[0], frames.device
+    return (torch.empty((rows, n, int(stride)), dtype=torch.uint8, device=dev),
+            [torch.empty((rows, n), dtype=torch.int64, device=dev) for _ in range(int64s)],
+            [torch.empty((rows, n), dtype=torch.int32, device=dev) for _ in range(int32s)])
+
+
 class Encoder:
     """icerx_encoder: frames of one geometry, many per call, buffers resident on one GPU."""
 
@@ -223,20 +186,17 @@ class Encoder:
                            d_rcs: int, stream: int = 0) -> None:
         rc = self.lib.icerx_encode_device(self.handle, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs,
                                           stream)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("icerx_encode_device", rc)
 
     def encode_device_async_ptrs(self, d_frames: int, n_frames: int, byte_quota: int, d_out: int, out_stride: int, d_sizes: int,
                                  d_rcs: int, stream: int = 0) -> None:
         """first half of encode_device_ptrs: returns once everything is enqueued; wait() completes it"""
         rc = self.lib.icerx_encode_device_async(self.handle, d_frames, n_frames, byte_quota, d_out, out_stride, d_sizes, d_rcs, stream)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device_async rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("icerx_encode_device_async", rc)
 
     def wait(self) -> None:
         rc = self.lib.icerx_encoder_wait(self.handle)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encoder_wait rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("icerx_encoder_wait", rc)
 
     def encode_torch(self, frames, byte_quota: int, out, sizes, rcs) -> None:
         """frames: cuda int16/uint16 tensor (n, channels, h, w) or (n, h, w); out: cuda uint8 (n, stride);
@@ -251,12 +211,9 @@ class Encoder:
                            stream: int = 0) -> None:
         """icerx_encode_device_ladder: the frames at every quota of `quotas` (at most ICERX_MAX_LADDER) in one call; frame f at
         quotas[q] goes to row q * n_frames + f of d_out and entry q * n_frames + f of d_sizes / d_rcs"""
-        qs = [int(q) for q in quotas]
-        arr = (C.c_size_t * max(len(qs), 1))(*qs)
-        rc = self.lib.icerx_encode_device_ladder(self.handle, d_frames, n_frames, arr, len(qs), d_out, out_stride, d_sizes, d_rcs,
-                                                 stream)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device_ladder rc={rc}: {self.lib.icerx_last_error().decode()}")
+        rc = self.lib.icerx_encode_device_ladder(self.handle, d_frames, n_frames, c_array(C.c_size_t, quotas), len(quotas), d_out, out_stride,
+                                                 d_sizes, d_rcs, stream)
+        _check("icerx_encode_device_ladder", rc)
 
     def encode_ladder_torch(self, frames, quotas, out=None, sizes=None, rcs=None):
         """frames: cuda tensor (n, channels, h, w) or (n, h, w) -- int16/uint16, or uint8 (int8 storage) for an encoder of
@@ -266,12 +223,9 @@ class Encoder:
         import torch
         n, Q = frames.shape[0], len(quotas)
         dev = frames.device
-        if out is None:
-            out = torch.empty((Q, n, max(int(q) for q in quotas)), dtype=torch.uint8, device=dev)
-        if sizes is None:
-            sizes = torch.empty((Q, n), dtype=torch.int64, device=dev)
-        if rcs is None:
-            rcs = torch.empty((Q, n), dtype=torch.int32, device=dev)
+        if out is None or sizes is None or rcs is None:
+            own_out, (own_sizes,), (own_rcs,) = _cut_outputs(frames, Q, max(int(q) for q in quotas) if out is None else 0)
+            out, sizes, rcs = (own_out if out is None else out), (own_sizes if sizes is None else sizes), (own_rcs if rcs is None else rcs)
         if out.dim() != 3 or tuple(out.shape[:2]) != (Q, n) or out.stride(2) != 1 or out.stride(0) != n * out.stride(1):
             raise ValueError("out must be a uint8 tensor (Q, n, stride) whose rows are stride bytes apart")
         if tuple(sizes.shape) != (Q, n) or tuple(rcs.shape) != (Q, n) or not sizes.is_contiguous() or not rcs.is_contiguous():
@@ -285,12 +239,9 @@ class Encoder:
         """icerx_encode_device_roi: the ladder's call with every frame's quota spent first inside its rectangle (d_rois: device,
         n_frames x 4 uint32 x, y, w, h), the foreground `shift` bit planes ahead; outputs quota-major as the ladder's, K to entry
         q * n_frames + f of d_kept, the frames' foreground units to d_foreground"""
-        qs = [int(q) for q in quotas]
-        arr = (C.c_size_t * max(len(qs), 1))(*qs)
-        rc = self.lib.icerx_encode_device_roi(self.handle, d_frames, n_frames, d_rois, int(shift), arr, len(qs), d_out, out_stride, d_sizes,
-                                              d_rcs, d_kept, d_foreground, stream)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device_roi rc={rc}: {self.lib.icerx_last_error().decode()}")
+        rc = self.lib.icerx_encode_device_roi(self.handle, d_frames, n_frames, d_rois, int(shift), c_array(C.c_size_t, quotas), len(quotas),
+                                              d_out, out_stride, d_sizes, d_rcs, d_kept, d_foreground, stream)
+        _check("icerx_encode_device_roi", rc)
 
     def encode_roi_torch(self, frames, rois, shift: int, quotas):
         """frames: as encode_ladder_torch takes them.  rois: cuda int32 or uint32 tensor (n, 4) on the frames' device -- x, y, w, h
@@ -302,9 +253,7 @@ class Encoder:
         if rois.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(rois.shape) != (n, 4) or rois.device != dev or \
                 not rois.is_contiguous():
             raise ValueError("rois must be a contiguous int32 or uint32 tensor (n, 4) on the frames' device")
-        out = torch.empty((Q, n, max(int(q) for q in quotas)), dtype=torch.uint8, device=dev)
-        sizes = torch.empty((Q, n), dtype=torch.int64, device=dev)
-        rcs, kept = (torch.empty((Q, n), dtype=torch.int32, device=dev) for _ in range(2))
+        out, (sizes,), (rcs, kept) = _cut_outputs(frames, Q, max(int(q) for q in quotas), int32s=2)
         foreground = torch.empty((n,), dtype=torch.int32, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         self.encode_roi_ptrs(frames.data_ptr(), n, rois.data_ptr(), shift, quotas, out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(),
@@ -315,12 +264,9 @@ class Encoder:
                            d_rcs: int, d_reached: int, d_dist: int, d_equiv_quota: int, stream: int = 0) -> None:
         """icerx_encode_device_target: every frame cut where each mean-squared-error target of `targets_mse` (at most
         ICERX_MAX_LADDER) is met, or at byte_cap; frame f at targets_mse[t] goes to row / entry t * n_frames + f of the outputs"""
-        ts = [float(t) for t in targets_mse]
-        arr = (C.c_double * max(len(ts), 1))(*ts)
-        rc = self.lib.icerx_encode_device_target(self.handle, d_frames, n_frames, arr, len(ts), byte_cap, d_out, out_stride, d_sizes, d_rcs,
-                                                 d_reached, d_dist, d_equiv_quota, stream)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device_target rc={rc}: {self.lib.icerx_last_error().decode()}")
+        rc = self.lib.icerx_encode_device_target(self.handle, d_frames, n_frames, c_array(C.c_double, targets_mse), len(targets_mse), byte_cap,
+                                                 d_out, out_stride, d_sizes, d_rcs, d_reached, d_dist, d_equiv_quota, stream)
+        _check("icerx_encode_device_target", rc)
 
     def encode_target_torch(self, frames, targets, byte_cap: int, psnr: bool = False):
         """frames: as encode_ladder_torch takes them.  targets: mean squared errors per sample, or with psnr=True peak
@@ -331,9 +277,7 @@ class Encoder:
         peak = float((1 << self.sample_bits) - 1)
         mse = [peak * peak / 10.0 ** (float(t) / 10.0) for t in targets] if psnr else [float(t) for t in targets]
         n, T, dev = frames.shape[0], len(mse), frames.device
-        out = torch.empty((T, n, int(byte_cap)), dtype=torch.uint8, device=dev)
-        sizes, dist, equiv = (torch.empty((T, n), dtype=torch.int64, device=dev) for _ in range(3))
-        rcs, reached = (torch.empty((T, n), dtype=torch.int32, device=dev) for _ in range(2))
+        out, (sizes, dist, equiv), (rcs, reached) = _cut_outputs(frames, T, byte_cap, int64s=3, int32s=2)
         st = torch.cuda.current_stream(dev).cuda_stream
         self.encode_target_ptrs(frames.data_ptr(), n, mse, int(byte_cap), out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(),
                                 reached.data_ptr(), dist.data_ptr(), equiv.data_ptr(), st)
@@ -344,12 +288,9 @@ class Encoder:
         """icerx_encode_device_budget: for each byte budget of `budgets` (at most ICERX_MAX_LADDER) the frames share it at one
         distortion threshold, no stream above byte_cap; frame f at budgets[b] goes to row / entry b * n_frames + f of the
         per-stream outputs, the threshold and the sum of the sizes to entry b of d_threshold / d_total"""
-        bs = [int(b) for b in budgets]
-        arr = (C.c_uint64 * max(len(bs), 1))(*bs)
-        rc = self.lib.icerx_encode_device_budget(self.handle, d_frames, n_frames, arr, len(bs), byte_cap, d_out, out_stride, d_sizes, d_rcs,
-                                                 d_at_cap, d_dist, d_equiv_quota, d_threshold, d_total, stream)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device_budget rc={rc}: {self.lib.icerx_last_error().decode()}")
+        rc = self.lib.icerx_encode_device_budget(self.handle, d_frames, n_frames, c_array(C.c_uint64, budgets), len(budgets), byte_cap, d_out,
+                                                 out_stride, d_sizes, d_rcs, d_at_cap, d_dist, d_equiv_quota, d_threshold, d_total, stream)
+        _check("icerx_encode_device_budget", rc)
 
     def encode_budget_torch(self, frames, budgets, byte_cap: int):
         """frames: as encode_ladder_torch takes them.  budgets: byte budgets for the whole batch.  Returns cuda tensors (out uint8
@@ -358,9 +299,7 @@ class Encoder:
         current stream."""
         import torch
         n, nb, dev = frames.shape[0], len(budgets), frames.device
-        out = torch.empty((nb, n, int(byte_cap)), dtype=torch.uint8, device=dev)
-        sizes, dist, equiv = (torch.empty((nb, n), dtype=torch.int64, device=dev) for _ in range(3))
-        rcs, at_cap = (torch.empty((nb, n), dtype=torch.int32, device=dev) for _ in range(2))
+        out, (sizes, dist, equiv), (rcs, at_cap) = _cut_outputs(frames, nb, byte_cap, int64s=3, int32s=2)
         threshold, total = (torch.empty((nb,), dtype=torch.int64, device=dev) for _ in range(2))
         st = torch.cuda.current_stream(dev).cuda_stream
         self.encode_budget_ptrs(frames.data_ptr(), n, budgets, int(byte_cap), out.data_ptr(), out.stride(1), sizes.data_ptr(), rcs.data_ptr(),
@@ -381,8 +320,7 @@ class Encoder:
             families = self.info()["units_per_frame"] // planes      # (a family = the coded planes of one rectangle, csrc/plan.hpp)
         dst = np.zeros((families, planes + 1), np.uint64)
         rc = self.lib.icerx_get_distortion_table(self.handle, frame, dst.ctypes.data, dst.size)
-        if rc != 0:
-            raise IcerHipError(f"icerx_get_distortion_table rc={rc}: no target call yet, or the frame was not part of the last one")
+        _check("icerx_get_distortion_table", rc, ": no target call yet, or the frame was not part of the last one")
         return dst
 
     def encode_torch_s8(self, planes, byte_quota: int):
@@ -397,8 +335,7 @@ class Encoder:
         st = torch.cuda.current_stream(planes.device).cuda_stream
         rc = self.lib.icerx_encode_device_s8(self.handle, planes.data_ptr(), n, byte_quota, out.data_ptr(), stride,
                                              sizes.data_ptr(), rcs.data_ptr(), st)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_device_s8 rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("icerx_encode_device_s8", rc)
         sz, rr, host = sizes.cpu().numpy(), rcs.cpu().numpy(), out.cpu().numpy()
         return [(int(rr[k]), bytes(host[k, : int(sz[k])])) for k in range(n)]
 
@@ -410,8 +347,7 @@ class Encoder:
         st = torch.cuda.current_stream(raw.device).cuda_stream
         rc = fn(self.handle, raw.data_ptr(), raw.shape[0], byte_quota, out.data_ptr(), out.stride(0), sizes.data_ptr(),
                 rcs.data_ptr(), st)
-        if rc != 0:
-            raise IcerHipError(f"front-end encode rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("front-end encode", rc)
 
     def encode_host(self, frames: np.ndarray, byte_quota: int):
         """frames: uint16 array (n, channels, h, w) or (n, h, w).  Returns list of (rc, stream bytes)."""
@@ -423,8 +359,7 @@ class Encoder:
         rcs = np.zeros(n, dtype=np.int32)
         rc = self.lib.icerx_encode_host(self.handle, frames.ctypes.data, n, byte_quota, out.ctypes.data, stride,
                                         sizes.ctypes.data, rcs.ctypes.data)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_host rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("icerx_encode_host", rc)
         return [(int(rcs[i]), bytes(out[i, : int(sizes[i])])) for i in range(n)]
 
     def encode_host_into(self, frames: np.ndarray, byte_quota: int, out: np.ndarray, sizes: np.ndarray, rcs: np.ndarray) -> None:
@@ -433,14 +368,12 @@ class Encoder:
         n = frames.shape[0]
         rc = self.lib.icerx_encode_host(self.handle, frames.ctypes.data, n, byte_quota, out.ctypes.data, out.shape[1],
                                         sizes.ctypes.data, rcs.ctypes.data)
-        if rc != 0:
-            raise IcerHipError(f"icerx_encode_host rc={rc}: {self.lib.icerx_last_error().decode()}")
+        _check("icerx_encode_host", rc)
 
     def coefficients(self, frame: int = 0, channel: int = 0) -> np.ndarray:
         dst = np.zeros((self.h, self.w), dtype=np.uint16)
         rc = self.lib.icerx_get_coefficients(self.handle, frame, channel, dst.ctypes.data)
-        if rc != 0:
-            raise IcerHipError(f"icerx_get_coefficients rc={rc}")
+        _check("icerx_get_coefficients", rc, "")
         return dst
 
     def timing_enable(self, on: bool = True) -> None:
@@ -450,8 +383,7 @@ class Encoder:
         ms = (C.c_double * ICERX_NUM_STAGES)()
         calls = C.c_uint64(0)
         rc = self.lib.icerx_timing_read(self.handle, ms, C.byref(calls), 1 if reset else 0)
-        if rc != 0:
-            raise IcerHipError(f"icerx_timing_read rc={rc}")
+        _check("icerx_timing_read", rc, "")
         return {n: ms[i] for i, n in enumerate(STAGE_NAMES)}, int(calls.value)
 
     def stats(self):
@@ -527,13 +459,11 @@ def _wavelet_host(lib, inverse: bool, data: np.ndarray, filt: int, stages: int, 
     bits = 16 if data.dtype == np.uint16 else 8
     pre = ("icer_inverse_wavelet_transform_" if inverse else "icer_wavelet_transform_") + kind + ("_uint16" if bits == 16 else "_uint8")
     fn = getattr(lib, pre)
-    fn.restype = C.c_int
     ptr = C.c_void_p(data.ctypes.data)
     if kind == "1d":
         N = data.size if N is None else int(N)
         if N >= 1 and (N - 1) * stride + 1 > data.size:
             raise ValueError("N samples at `stride` run past the array")
-        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
         return fn(ptr, N, stride, filt)
     h, w = data.shape[-2:] if data.ndim >= 2 else (1, data.size)
     image_w = w if image_w is None else int(image_w)
@@ -541,12 +471,10 @@ def _wavelet_host(lib, inverse: bool, data: np.ndarray, filt: int, stages: int, 
     if kind == "stages":
         if image_w * image_h > data.size:
             raise ValueError("image_w * image_h runs past the array")
-        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint8, C.c_int]
         return fn(ptr, image_w, image_h, stages, filt)
     rowstride = w if rowstride is None else int(rowstride)
     if image_h >= 1 and image_w >= 1 and (image_h - 1) * rowstride + image_w > data.size:
         raise ValueError("the image_w x image_h region at `rowstride` runs past the array")
-    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     return fn(ptr, image_w, image_h, rowstride, filt)
 
 
@@ -568,17 +496,12 @@ def _wavelet_torch(fn, planes, stages: int, filt: int):
     h, w = planes.shape[-2:]
     n = planes.numel() // (h * w)
     lib = load_library()
-    lib.icerx_wavelet_workspace_bytes.restype = C.c_size_t
-    lib.icerx_wavelet_workspace_bytes.argtypes = [C.c_size_t, C.c_size_t, C.c_int, C.c_int]
     ws = torch.empty(int(lib.icerx_wavelet_workspace_bytes(w, h, n, bits)), dtype=torch.uint8, device=planes.device)
     rcs = torch.zeros(n, dtype=torch.int32, device=planes.device)
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     with torch.cuda.device(planes.device):
         st = torch.cuda.current_stream(planes.device).cuda_stream
         rc = fn(planes.data_ptr(), n, w, h, w * h, stages, filt, bits, ws.data_ptr(), rcs.data_ptr(), st)
-    if rc:
-        raise IcerHipError(f"wavelet transform rc={rc}")
+    _check("wavelet transform", rc, "")
     return rcs
 
 

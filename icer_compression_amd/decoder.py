@@ -18,6 +18,8 @@ import os
 
 import numpy as np
 
+from ._abi import DECODER, c_array, declare
+
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libicer_hip_dec.so")
 ICER_DECODER_OUT_OF_DATA = -7
@@ -25,74 +27,76 @@ ICER_DECODED_INVALID_DATA = -8
 
 _lib = None
 _sz = C.c_size_t
-_u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 
 
 def bind(path: str) -> C.CDLL:
     """dlopen a build of the decoder library (RTLD_LOCAL: it exports the same icer_* names as the reference) and declare
-    its entry points.  (tests/test_emu_decoder.py binds a CPU mock build of decoder.hip's host pipeline this way.)"""
-    lib = C.CDLL(path, mode=os.RTLD_LOCAL)
-    lib.icer_get_image_dimensions.argtypes = [_u8p, _sz, C.POINTER(_sz), C.POINTER(_sz)]
-    tail = [C.POINTER(_sz), C.POINTER(_sz), _sz, _u8p, _sz, C.c_uint8, C.c_int, C.c_uint8]
-    for name, n in (("icer_decompress_image_uint16", 1), ("icer_decompress_image_yuv_uint16", 3),
-                    ("icer_decompress_image_uint8", 1), ("icer_decompress_image_yuv_uint8", 3)):
-        getattr(lib, name).argtypes = [C.c_void_p] * n + tail
-    lib.icerx_decoder_last_error.restype = C.c_char_p
-    # the display entry points (a build without them still serves everything above)
-    if hasattr(lib, "icerx_decompress_display"):
-        lib.icerx_decompress_display.argtypes = [C.c_void_p] + tail + [C.c_int]
-        lib.icerx_planes_to_display_device.argtypes = [C.c_void_p, C.c_int, C.c_int, _sz, _sz, _sz, C.c_int, C.c_void_p, _sz, C.c_void_p]
-        disp = [C.POINTER(_sz), C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(C.c_int), C.POINTER(_sz), C.POINTER(_sz)]
-        lib.icerx_decode_host_display.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + disp
-        lib.icerx_decode_device_display.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + disp
-    if hasattr(lib, "icerx_decode_device_display_async"):
-        lib.icerx_decode_display_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, _sz]
-        lib.icerx_decode_display_workspace_bytes.restype = _sz
-        lib.icerx_decode_device_display_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, _sz,
-                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
-    # decoding at 1/2^r resolution
-    if hasattr(lib, "icerx_decoder_create_reduced"):
-        lib.icerx_decoder_create_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
-        lib.icerx_decoder_reduce.argtypes = [C.c_void_p]
-        lib.icerx_reduced_size.argtypes = [_sz, _sz, C.c_int, C.POINTER(_sz), C.POINTER(_sz)]
-        lib.icerx_reduced_size.restype = None
-        lib.icerx_decompress_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int] + tail + [C.c_int, C.c_int]
-    # truncated coefficients rebuilt inside their interval
-    if hasattr(lib, "icerx_decoder_set_reconstruction"):
-        lib.icerx_decoder_set_reconstruction.argtypes = [C.c_void_p, C.c_int]
-        lib.icerx_decoder_reconstruction.argtypes = [C.c_void_p]
-        lib.icerx_decompress_reconstructed.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(_sz), C.POINTER(_sz), _sz, _u8p, _sz,
-                                                       C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]
-    # re-cutting by resolution as well as by byte quota
-    if hasattr(lib, "icerx_recut_device_cuts_async"):
-        lib.icerx_recutter_create_reduced.argtypes = [C.POINTER(C.c_void_p), C.c_int, _sz, _sz, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
-        lib.icerx_recutter_max_reduce.argtypes = [C.c_void_p]
-        lib.icerx_recut_cuts_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, C.c_int]
-        lib.icerx_recut_cuts_workspace_bytes.restype = _sz
-        lib.icerx_recut_device_cuts_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_int),
-                                                      C.POINTER(_sz), C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
-                                                      C.c_void_p]
-    # re-cutting by region of interest, at any resolution
-    if hasattr(lib, "icerx_recut_device_roi_async"):
-        lib.icerx_recut_roi_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, C.c_int]
-        lib.icerx_recut_roi_workspace_bytes.restype = _sz
-        lib.icerx_recut_device_roi_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p,
-                                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz), C.c_int, C.c_void_p, _sz,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
-    # refinement increments: the difference and the union of two stored streams
-    if hasattr(lib, "icerx_combine_device_async"):
-        lib.icerx_combine_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz]
-        lib.icerx_combine_workspace_bytes.restype = _sz
-        lib.icerx_combine_device_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p,
-                                                   _sz, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   _sz, C.c_void_p]
-    return lib
+    its entry points.  (tests/test_emu_decoder.py binds a CPU mock build of decoder.hip's host pipeline this way; a build
+    without some of the entry points still serves the others.)"""
+    return declare(C.CDLL(path, mode=os.RTLD_LOCAL), DECODER)
 
 
 def _need(lib, name):
     if not hasattr(lib, name):
         raise RuntimeError(f"this build of the decoder library has no {name}")
     return getattr(lib, name)
+
+
+def _check(lib, name, rc):
+    if rc != 0:
+        raise RuntimeError(f"{name}: {rc} {lib.icerx_decoder_last_error().decode()}")
+
+
+# ---- the one path behind the *_torch methods --------------------------------------------------------------------------
+def _stream_stride(data, stream_stride, offsets, any_rows=False) -> int:
+    """stream_stride as given; else 0 when every operand has offsets; else the row stride of a blob with rows (a 2-D blob;
+    any_rows: a blob of two or more dimensions, its stride(-2))"""
+    if stream_stride is not None:
+        return int(stream_stride)
+    for o in offsets:
+        if o is None:
+            if data.dim() < 2 or (data.dim() != 2 and not any_rows):
+                raise ValueError("a 1-D blob needs offsets or stream_stride")
+            return data.stride(-2)
+    return 0
+
+
+def _need_tensors(*named):
+    """(name, tensor, dtype or dtypes) in turn: a contiguous cuda tensor of one of the dtypes; None (offsets not given) passes"""
+    for name, t, dts in named:
+        dts = dts if isinstance(dts, tuple) else (dts,)
+        if t is not None and (not t.is_cuda or not t.is_contiguous() or t.dtype not in dts):
+            raise ValueError(f"{name}: a contiguous cuda {dts[0]} tensor is needed")
+
+
+def _enqueue(lib, name, cache, need, device, ptrs_call, *args):
+    """ptrs_call(*args, workspace, its bytes, stream) on torch's current stream, tensors among args as their data_ptr(): the
+    stream's workspace comes out of `cache`, grown to max(need, 1) bytes here, on the host; a refused call raises"""
+    import torch
+    st = torch.cuda.current_stream(device)
+    work = cache.get(st.cuda_stream)
+    if work is None or work.numel() < max(need, 1):
+        work = cache[st.cuda_stream] = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    work.record_stream(st)
+    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    _check(lib, name, ptrs_call(*args, work.data_ptr(), work.numel(), st.cuda_stream))
+
+
+def _bytes_through(streams, rows, stride, call):
+    """bytes in, bytes out: the streams in one blob on the current device, zeroed outputs of `rows` rows of `stride` bytes,
+    call(blob, lens, offsets, out, sizes, rcs), a wait, and -> [(rc, stream)] per row"""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    lens = [len(s) for s in streams]
+    blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    out = torch.zeros((rows, stride), dtype=torch.uint8, device=dev)
+    sizes = torch.zeros(rows, dtype=torch.int64, device=dev)
+    rcs = torch.zeros(rows, dtype=torch.int32, device=dev)
+    call(torch.from_numpy(blob).to(dev), torch.tensor(lens, dtype=torch.int64, device=dev), torch.from_numpy(offs).to(dev), out, sizes, rcs)
+    torch.cuda.current_stream(dev).synchronize()
+    out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
+    return [(int(rcs[k]), out[k, : int(sizes[k])].tobytes()) for k in range(rows)]
 
 
 def load_library() -> C.CDLL:
@@ -203,8 +207,7 @@ def planes_to_display_torch(planes):
     if n:
         st = torch.cuda.current_stream(planes.device)
         rc = fn(planes.data_ptr(), n, ch, w, h, h * w, 8 if planes.dtype == torch.uint8 else 16, out.data_ptr(), h * w, st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_planes_to_display_device: {rc} {load_library().icerx_decoder_last_error().decode()}")
+        _check(load_library(), "icerx_planes_to_display_device", rc)
     return out
 
 
@@ -219,33 +222,16 @@ class Decoder:
         call of this decoder (icerx_decoder_set_reconstruction; 3 is the recommended value, 0 the reference's decode)"""
         self.lib = lib or load_library()
         self.channels, self.bits, self.reduce = channels, bits, 0
-        self.lib.icerx_decoder_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int]
-        self.lib.icerx_decoder_destroy.argtypes = [C.c_void_p]
-        self.lib.icerx_decoder_destroy.restype = None
-        tail = [C.POINTER(_sz), C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(C.c_int), C.POINTER(_sz), C.POINTER(_sz)]
-        self.lib.icerx_decode_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + tail
-        self.lib.icerx_decode_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + tail
-        if hasattr(self.lib, "icerx_decode_device_async"):
-            self.lib.icerx_decode_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, _sz]
-            self.lib.icerx_decode_workspace_bytes.restype = _sz
-            self.lib.icerx_decode_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p,
-                                                           C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _sz,
-                                                           C.c_void_p]
         self._workspaces = {}                # decode_torch: one cached workspace per torch stream
         self._display_workspaces = {}        # decode_display_torch: the same, sized for the display call
         self.handle = C.c_void_p()
         if reduce != 0:
             fn = _need(self.lib, "icerx_decoder_create_reduced")
-            fn.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int]
-            self.lib.icerx_decoder_reduce.argtypes = [C.c_void_p]
-            rc = fn(C.byref(self.handle), device, channels, stages, filt, segments, bits, reduce)
-            if rc != 0:
-                raise RuntimeError(f"icerx_decoder_create_reduced: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+            _check(self.lib, "icerx_decoder_create_reduced", fn(C.byref(self.handle), device, channels, stages, filt, segments, bits, reduce))
             self.reduce = int(self.lib.icerx_decoder_reduce(self.handle))
         else:
             rc = self.lib.icerx_decoder_create(C.byref(self.handle), device, channels, stages, filt, segments, bits)
-            if rc != 0:
-                raise RuntimeError(f"icerx_decoder_create: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+            _check(self.lib, "icerx_decoder_create", rc)
         if reconstruct != 0:
             self.set_reconstruction(reconstruct)
 
@@ -254,14 +240,11 @@ class Decoder:
         """the decoder's reconstruction point in eighths (icerx_decoder_reconstruction; 0 on a build without it)"""
         if not hasattr(self.lib, "icerx_decoder_reconstruction"):
             return 0
-        self.lib.icerx_decoder_reconstruction.argtypes = [C.c_void_p]
         return int(self.lib.icerx_decoder_reconstruction(self.handle))
 
     def set_reconstruction(self, eighths: int) -> None:
         """icerx_decoder_set_reconstruction: 0..4, for every call enqueued from now on"""
-        fn = _need(self.lib, "icerx_decoder_set_reconstruction")
-        fn.argtypes = [C.c_void_p, C.c_int]
-        rc = fn(self.handle, eighths)
+        rc = _need(self.lib, "icerx_decoder_set_reconstruction")(self.handle, eighths)
         if rc != 0:
             raise ValueError(f"icerx_decoder_set_reconstruction({eighths}): {rc}")
 
@@ -283,24 +266,30 @@ class Decoder:
         n = len(streams)
         return blob, (_sz * n)(*[int(o) for o in offs]), (_sz * n)(*lens)
 
+    def _sync(self, fn, n: int, data: int, offsets, lens, out, frame_stride: int):
+        """one of the four synchronous calls, its per-frame host arrays packed here; -> (rc, rcs, ws, hs)"""
+        m = max(n, 1)
+        offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
+        rcs, ws, hs = (C.c_int * m)(), (_sz * m)(), (_sz * m)()
+        rc = fn(self.handle, n, data, offs, ln, out, frame_stride, rcs, ws, hs)
+        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+
+    def _sync_host(self, fn, streams, frame_stride: int, arrays):
+        """the same for streams in host memory, written to the host arrays `arrays` (in frame order)"""
+        blob, offs, lens = self._pack(streams)
+        ptrs = (C.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
+        return self._sync(fn, len(streams), blob.ctypes.data, offs, lens, ptrs, frame_stride)
+
     def decode_host(self, streams, frame_stride: int):
         """-> (rc, [(rc_k, w_k, h_k, [flat planes])]) for a list of streams in host memory"""
-        n = len(streams)
-        blob, offs, lens = self._pack(streams)
-        dt = np.uint16 if self.bits == 16 else np.uint8
-        planes = [np.zeros(max(frame_stride, 1), dt) for _ in range(n * self.channels)]
-        ptrs = (C.c_void_p * max(len(planes), 1))(*[p.ctypes.data for p in planes])
-        rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
-        rc = self.lib.icerx_decode_host(self.handle, n, blob.ctypes.data, offs, lens, ptrs, frame_stride, rcs, ws, hs)
-        return rc, [(rcs[k], ws[k], hs[k], planes[k * self.channels: (k + 1) * self.channels]) for k in range(n)]
+        n, ch = len(streams), self.channels
+        planes = [np.zeros(max(frame_stride, 1), np.uint16 if self.bits == 16 else np.uint8) for _ in range(n * ch)]
+        rc, rcs, ws, hs = self._sync_host(self.lib.icerx_decode_host, streams, frame_stride, planes)
+        return rc, [(rcs[k], ws[k], hs[k], planes[k * ch: (k + 1) * ch]) for k in range(n)]
 
     def decode_device(self, n: int, d_data: int, offsets, lens, d_out: int, frame_stride: int):
         """raw device pointers (e.g. torch tensors' data_ptr()); -> (rc, rcs, ws, hs)"""
-        offs = (_sz * max(n, 1))(*[int(o) for o in offsets])
-        ln = (_sz * max(n, 1))(*[int(x) for x in lens])
-        rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
-        rc = self.lib.icerx_decode_device(self.handle, n, d_data, offs, ln, d_out, frame_stride, rcs, ws, hs)
-        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+        return self._sync(self.lib.icerx_decode_device, n, d_data, offsets, lens, d_out, frame_stride)
 
     def workspace_bytes(self, n: int, data_bytes: int, frame_stride: int) -> int:
         """icerx_decode_workspace_bytes: the device workspace one decode_device_async_ptrs call needs"""
@@ -319,23 +308,14 @@ class Decoder:
         """icerx_decode_host_display -> (rc, [(rc_k, w_k, h_k, image)]): image = flat uint8 of channels * frame_stride bytes,
         its first channels * w_k * h_k bytes the gray8 / RGB888 image of frame k"""
         fn = _need(self.lib, "icerx_decode_host_display")
-        n = len(streams)
-        blob, offs, lens = self._pack(streams)
-        images = [np.zeros(max(self.channels * frame_stride, 1), np.uint8) for _ in range(n)]
-        ptrs = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in images])
-        rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
-        rc = fn(self.handle, n, blob.ctypes.data, offs, lens, ptrs, frame_stride, rcs, ws, hs)
-        return rc, [(rcs[k], ws[k], hs[k], images[k]) for k in range(n)]
+        images = [np.zeros(max(self.channels * frame_stride, 1), np.uint8) for _ in streams]
+        rc, rcs, ws, hs = self._sync_host(fn, streams, frame_stride, images)
+        return rc, list(zip(rcs, ws, hs, images))
 
     def decode_display_device(self, n: int, d_data: int, offsets, lens, d_out: int, frame_stride: int):
         """icerx_decode_device_display on raw device pointers; frame k's image at d_out + k * channels * frame_stride bytes
         -> (rc, rcs, ws, hs)"""
-        fn = _need(self.lib, "icerx_decode_device_display")
-        offs = (_sz * max(n, 1))(*[int(o) for o in offsets])
-        ln = (_sz * max(n, 1))(*[int(x) for x in lens])
-        rcs, ws, hs = (C.c_int * max(n, 1))(), (_sz * max(n, 1))(), (_sz * max(n, 1))()
-        rc = fn(self.handle, n, d_data, offs, ln, d_out, frame_stride, rcs, ws, hs)
-        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+        return self._sync(_need(self.lib, "icerx_decode_device_display"), n, d_data, offsets, lens, d_out, frame_stride)
 
     def display_workspace_bytes(self, n: int, data_bytes: int, frame_stride: int) -> int:
         """icerx_decode_display_workspace_bytes: the device workspace one decode_display_async_ptrs call needs"""
@@ -356,31 +336,15 @@ class Decoder:
         (which holds the working planes) is cached per stream, apart from decode_torch's."""
         import torch
         n = int(lens.shape[0])
-        if offsets is None and stream_stride is None:
-            if data.dim() != 2:
-                raise ValueError("a 1-D blob needs offsets or stream_stride")
-            stream_stride = data.stride(0)
-        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("rcs", rcs, torch.int32),
-                            ("ws", ws, torch.int64), ("hs", hs, torch.int64), ("out", out, torch.uint8)) + \
-                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
-                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("rcs", rcs, torch.int32), ("ws", ws, torch.int64),
+                      ("hs", hs, torch.int64), ("out", out, torch.uint8), ("offsets", offsets, torch.int64))
         if n and out.numel() % (n * self.channels):
             raise ValueError("out must hold n * frame_stride * channels bytes")
         frame_stride = out.numel() // (n * self.channels) if n else 0
-        data_bytes = data.numel()
-        st = torch.cuda.current_stream(data.device)
-        need = self.display_workspace_bytes(n, data_bytes, frame_stride) if n else 0
-        work = self._display_workspaces.get(st.cuda_stream)
-        if work is None or work.numel() < max(need, 1):
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
-            self._display_workspaces[st.cuda_stream] = work
-        work.record_stream(st)
-        rc = self.decode_display_async_ptrs(n, data.data_ptr(), data_bytes, offsets.data_ptr() if offsets is not None else None,
-                                            int(stream_stride or 0), lens.data_ptr(), out.data_ptr(), frame_stride, rcs.data_ptr(),
-                                            ws.data_ptr(), hs.data_ptr(), work.data_ptr(), work.numel(), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_decode_device_display_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+        need = self.display_workspace_bytes(n, data.numel(), frame_stride) if n else 0
+        _enqueue(self.lib, "icerx_decode_device_display_async", self._display_workspaces, need, data.device, self.decode_display_async_ptrs,
+                 n, data, data.numel(), offsets, stream_stride, lens, out, frame_stride, rcs, ws, hs)
 
     def decode_torch(self, data, lens, out, rcs, ws, hs, offsets=None, stream_stride=None) -> None:
         """Decode n streams of a cuda uint8 tensor on torch's current stream, without waiting (icerx_decode_device_async).
@@ -398,32 +362,16 @@ class Decoder:
         """
         import torch
         n = int(lens.shape[0])
-        if offsets is None and stream_stride is None:
-            if data.dim() != 2:
-                raise ValueError("a 1-D blob needs offsets or stream_stride")
-            stream_stride = data.stride(0)
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
         want = (torch.int16, getattr(torch, "uint16", torch.int16)) if self.bits == 16 else (torch.uint8,)
-        for name, t, dts in (("data", data, (torch.uint8,)), ("lens", lens, (torch.int64,)), ("rcs", rcs, (torch.int32,)),
-                             ("ws", ws, (torch.int64,)), ("hs", hs, (torch.int64,)), ("out", out, want)) + \
-                ((("offsets", offsets, (torch.int64,)),) if offsets is not None else ()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype not in dts:
-                raise ValueError(f"{name}: a contiguous cuda {dts[0]} tensor is needed")
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("rcs", rcs, torch.int32), ("ws", ws, torch.int64),
+                      ("hs", hs, torch.int64), ("out", out, want), ("offsets", offsets, torch.int64))
         if n and out.numel() % (n * self.channels):
             raise ValueError("out must hold n * channels * frame_stride samples")
         frame_stride = out.numel() // (n * self.channels) if n else 0
-        data_bytes = data.numel()
-        st = torch.cuda.current_stream(data.device)
-        need = self.workspace_bytes(n, data_bytes, frame_stride) if n else 0
-        work = self._workspaces.get(st.cuda_stream)
-        if work is None or work.numel() < max(need, 1):
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
-            self._workspaces[st.cuda_stream] = work
-        work.record_stream(st)
-        rc = self.decode_device_async_ptrs(n, data.data_ptr(), data_bytes, offsets.data_ptr() if offsets is not None else None,
-                                           int(stream_stride or 0), lens.data_ptr(), out.data_ptr(), frame_stride, rcs.data_ptr(),
-                                           ws.data_ptr(), hs.data_ptr(), work.data_ptr(), work.numel(), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_decode_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+        need = self.workspace_bytes(n, data.numel(), frame_stride) if n else 0
+        _enqueue(self.lib, "icerx_decode_device_async", self._workspaces, need, data.device, self.decode_device_async_ptrs,
+                 n, data, data.numel(), offsets, stream_stride, lens, out, frame_stride, rcs, ws, hs)
 
 
 MAX_LADDER = 16                  # ICERX_MAX_LADDER
@@ -443,17 +391,9 @@ class Recutter:
     def __init__(self, w: int, h: int, channels: int, stages: int, segments: int, bits: int = 16, device: int = -1, lib=None,
                  max_reduce: int = 0):
         self.lib = lib or load_library()
-        if not hasattr(self.lib, "icerx_recut_device_async"):
-            raise RuntimeError("this build of the decoder library has no icerx_recut_device_async")
+        _need(self.lib, "icerx_recut_device_async")
         self.w, self.h, self.channels, self.bits = w, h, channels, bits
         L = self.lib
-        L.icerx_recutter_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, _sz, _sz, C.c_int, C.c_int, C.c_uint, C.c_int]
-        L.icerx_recutter_destroy.argtypes = [C.c_void_p]
-        L.icerx_recutter_destroy.restype = None
-        L.icerx_recut_workspace_bytes.argtypes = [C.c_void_p, C.c_int, _sz, C.c_int]
-        L.icerx_recut_workspace_bytes.restype = _sz
-        L.icerx_recut_device_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _sz, C.c_void_p, _sz, C.c_void_p, C.POINTER(_sz),
-                                               C.c_int, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p]
         self._workspaces = {}                # recut_torch: one cached workspace per torch stream
         self._cuts_workspaces = {}           # recut_cuts_torch: the same, sized for the cuts call
         self._roi_workspaces = {}            # recut_roi_torch: the same, sized for the ROI call
@@ -462,14 +402,10 @@ class Recutter:
         self.max_reduce = 0
         if max_reduce != 0:
             fn = _need(L, "icerx_recutter_create_reduced")
-            rc = fn(C.byref(self.handle), device, w, h, channels, stages, segments, bits, max_reduce)
-            if rc != 0:
-                raise RuntimeError(f"icerx_recutter_create_reduced: {rc} {L.icerx_decoder_last_error().decode()}")
+            _check(L, "icerx_recutter_create_reduced", fn(C.byref(self.handle), device, w, h, channels, stages, segments, bits, max_reduce))
             self.max_reduce = int(L.icerx_recutter_max_reduce(self.handle))
             return
-        rc = L.icerx_recutter_create(C.byref(self.handle), device, w, h, channels, stages, segments, bits)
-        if rc != 0:
-            raise RuntimeError(f"icerx_recutter_create: {rc} {L.icerx_decoder_last_error().decode()}")
+        _check(L, "icerx_recutter_create", L.icerx_recutter_create(C.byref(self.handle), device, w, h, channels, stages, segments, bits))
 
     def close(self):
         if self.handle:
@@ -497,10 +433,9 @@ class Recutter:
         sizes: uint64 / int64; rcs: int32; quotas: a host sequence, None for a null pointer).  Frame f at quota q is row
         q * n + f of d_out and entry q * n + f of d_sizes / d_rcs.  Enqueues on `stream` and returns the call's rc without
         waiting."""
-        arr = None if quotas is None else (_sz * max(len(quotas), 1))(*[int(q) for q in quotas])
         nq = n_quotas if n_quotas is not None else (len(quotas) if quotas is not None else 0)
-        return self.lib.icerx_recut_device_async(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, arr, nq, d_out,
-                                                 out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, stream)
+        return self.lib.icerx_recut_device_async(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, c_array(_sz, quotas),
+                                                 nq, d_out, out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, stream)
 
     def recut_torch(self, data, lens, quotas, out, sizes, rcs, offsets=None, stream_stride=None) -> None:
         """Re-cut n masters of a cuda uint8 tensor to every quota of `quotas` on torch's current stream, without waiting.
@@ -513,48 +448,21 @@ class Recutter:
         is enqueued."""
         import torch
         n, Q = int(lens.shape[0]), len(quotas)
-        if offsets is None and stream_stride is None:
-            if data.dim() != 2:
-                raise ValueError("a 1-D blob needs offsets or stream_stride")
-            stream_stride = data.stride(0)
-        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8),
-                            ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32)) + \
-                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
-                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8), ("sizes", sizes, torch.int64),
+                      ("rcs", rcs, torch.int32), ("offsets", offsets, torch.int64))
         if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or sizes.numel() != Q * n or rcs.numel() != Q * n:
             raise ValueError("out must be (Q * n, out_stride), sizes and rcs Q * n entries")
-        st = torch.cuda.current_stream(data.device)
-        need = self.workspace_bytes(n, data.numel(), Q)
-        work = self._workspaces.get(st.cuda_stream)
-        if work is None or work.numel() < max(need, 1):
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
-            self._workspaces[st.cuda_stream] = work
-        work.record_stream(st)
-        rc = self.recut_device_async_ptrs(n, data.data_ptr(), data.numel(), offsets.data_ptr() if offsets is not None else None,
-                                          int(stream_stride or 0), lens.data_ptr(), quotas, out.data_ptr(), out.shape[-1],
-                                          sizes.data_ptr(), rcs.data_ptr(), work.data_ptr(), work.numel(), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_recut_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+        _enqueue(self.lib, "icerx_recut_device_async", self._workspaces, self.workspace_bytes(n, data.numel(), Q), data.device,
+                 self.recut_device_async_ptrs, n, data, data.numel(), offsets, stream_stride, lens, list(quotas), out, out.shape[-1], sizes, rcs)
 
     def recut(self, streams, quotas):
         """bytes in, bytes out: res[q][f] = (rc, stream) of master streams[f] re-cut to quotas[q] (copies to the device and back,
         and waits: a convenience, not the fast path)"""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
         n, Q = len(streams), len(quotas)
-        lens = [len(s) for s in streams]
-        blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-        stride = max(max(int(q) for q in quotas), 1)
-        out = torch.zeros((Q * n, stride), dtype=torch.uint8, device=dev)
-        sizes = torch.zeros(Q * n, dtype=torch.int64, device=dev)
-        rcs = torch.zeros(Q * n, dtype=torch.int32, device=dev)
-        self.recut_torch(torch.from_numpy(blob).to(dev), torch.tensor(lens, dtype=torch.int64, device=dev), quotas, out, sizes, rcs,
-                         offsets=torch.from_numpy(offs).to(dev))
-        torch.cuda.current_stream(dev).synchronize()
-        out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
-        return [[(int(rcs[q * n + f]), out[q * n + f, : int(sizes[q * n + f])].tobytes()) for f in range(n)] for q in range(Q)]
+        rows = _bytes_through(streams, Q * n, max(max(int(q) for q in quotas), 1), lambda blob, lens, offs, out, sizes, rcs:
+                              self.recut_torch(blob, lens, quotas, out, sizes, rcs, offsets=offs))
+        return [rows[q * n: (q + 1) * n] for q in range(Q)]
 
     # ---- cuts by resolution as well as by byte quota (icerx_recut_device_cuts_async) ----
     def cuts_workspace_bytes(self, n: int, data_bytes: int, n_cuts: int) -> int:
@@ -568,11 +476,9 @@ class Recutter:
         sequences of one length, None for a null pointer).  Frame f at cut c is row c * n + f of d_out and entry c * n + f of
         d_sizes / d_rcs.  Enqueues on `stream` and returns the call's rc without waiting."""
         fn = _need(self.lib, "icerx_recut_device_cuts_async")
-        red = None if reduces is None else (C.c_int * max(len(reduces), 1))(*[int(r) for r in reduces])
-        arr = None if quotas is None else (_sz * max(len(quotas), 1))(*[int(q) for q in quotas])
         nc = n_cuts if n_cuts is not None else (len(quotas) if quotas is not None else 0)
-        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, red, arr, nc, d_out, out_stride, d_sizes, d_rcs,
-                  d_workspace, workspace_bytes, stream)
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, c_array(C.c_int, reduces), c_array(_sz, quotas), nc,
+                  d_out, out_stride, d_sizes, d_rcs, d_workspace, workspace_bytes, stream)
 
     def recut_cuts_torch(self, data, lens, cuts, out, sizes, rcs, offsets=None, stream_stride=None) -> None:
         """recut_torch with cuts = [(reduce, quota), ...] in place of the quotas: row and entry c * n + f hold frame f at cuts[c],
@@ -581,49 +487,22 @@ class Recutter:
         recut_torch's."""
         import torch
         n, Q = int(lens.shape[0]), len(cuts)
-        if offsets is None and stream_stride is None:
-            if data.dim() != 2:
-                raise ValueError("a 1-D blob needs offsets or stream_stride")
-            stream_stride = data.stride(0)
-        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8),
-                            ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32)) + \
-                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
-                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8), ("sizes", sizes, torch.int64),
+                      ("rcs", rcs, torch.int32), ("offsets", offsets, torch.int64))
         if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or sizes.numel() != Q * n or rcs.numel() != Q * n:
             raise ValueError("out must be (Q * n, out_stride), sizes and rcs Q * n entries")
-        st = torch.cuda.current_stream(data.device)
-        need = self.cuts_workspace_bytes(n, data.numel(), Q)
-        work = self._cuts_workspaces.get(st.cuda_stream)
-        if work is None or work.numel() < max(need, 1):
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
-            self._cuts_workspaces[st.cuda_stream] = work
-        work.record_stream(st)
-        rc = self.recut_cuts_device_async_ptrs(n, data.data_ptr(), data.numel(), offsets.data_ptr() if offsets is not None else None,
-                                               int(stream_stride or 0), lens.data_ptr(), [c[0] for c in cuts], [c[1] for c in cuts],
-                                               out.data_ptr(), out.shape[-1], sizes.data_ptr(), rcs.data_ptr(), work.data_ptr(),
-                                               work.numel(), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_recut_device_cuts_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+        _enqueue(self.lib, "icerx_recut_device_cuts_async", self._cuts_workspaces, self.cuts_workspace_bytes(n, data.numel(), Q), data.device,
+                 self.recut_cuts_device_async_ptrs, n, data, data.numel(), offsets, stream_stride, lens, [c[0] for c in cuts],
+                 [c[1] for c in cuts], out, out.shape[-1], sizes, rcs)
 
     def recut_cuts(self, streams, cuts):
         """bytes in, bytes out: res[c][f] = (rc, stream) of master streams[f] at cuts[c] = (reduce, quota) (copies to the device
         and back, and waits: a convenience, not the fast path)"""
-        import torch
-        dev = torch.device("cuda", torch.cuda.current_device())
         n, Q = len(streams), len(cuts)
-        lens = [len(s) for s in streams]
-        blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-        stride = max(max(int(q) for _, q in cuts), 1)
-        out = torch.zeros((Q * n, stride), dtype=torch.uint8, device=dev)
-        sizes = torch.zeros(Q * n, dtype=torch.int64, device=dev)
-        rcs = torch.zeros(Q * n, dtype=torch.int32, device=dev)
-        self.recut_cuts_torch(torch.from_numpy(blob).to(dev), torch.tensor(lens, dtype=torch.int64, device=dev), cuts, out, sizes, rcs,
-                              offsets=torch.from_numpy(offs).to(dev))
-        torch.cuda.current_stream(dev).synchronize()
-        out, sizes, rcs = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy()
-        return [[(int(rcs[c * n + f]), out[c * n + f, : int(sizes[c * n + f])].tobytes()) for f in range(n)] for c in range(Q)]
+        rows = _bytes_through(streams, Q * n, max(max(int(q) for _, q in cuts), 1), lambda blob, lens, offs, out, sizes, rcs:
+                              self.recut_cuts_torch(blob, lens, cuts, out, sizes, rcs, offsets=offs))
+        return [rows[c * n: (c + 1) * n] for c in range(Q)]
 
     # ---- cuts by region of interest, at any resolution (icerx_recut_device_roi_async) ----
     def roi_workspace_bytes(self, n: int, data_bytes: int, n_cuts: int) -> int:
@@ -638,12 +517,10 @@ class Recutter:
         reduces None: every reduce 0; d_kept / d_foreground: uint32, entry c * n + f as d_sizes).  Enqueues on `stream` and
         returns the call's rc without waiting."""
         fn = _need(self.lib, "icerx_recut_device_roi_async")
-        red = None if reduces is None else (C.c_int * max(len(reduces), 1))(*[int(r) for r in reduces])
-        shf = None if shifts is None else (C.c_int * max(len(shifts), 1))(*[int(x) for x in shifts])
-        arr = None if quotas is None else (_sz * max(len(quotas), 1))(*[int(q) for q in quotas])
         nc = n_cuts if n_cuts is not None else (len(quotas) if quotas is not None else 0)
-        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_rois, red, shf, arr, nc, d_out, out_stride,
-                  d_sizes, d_rcs, d_kept, d_foreground, d_workspace, workspace_bytes, stream)
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_rois, c_array(C.c_int, reduces),
+                  c_array(C.c_int, shifts), c_array(_sz, quotas), nc, d_out, out_stride, d_sizes, d_rcs, d_kept, d_foreground, d_workspace,
+                  workspace_bytes, stream)
 
     def recut_roi_torch(self, data, lens, rois, cuts, out, sizes, rcs, kept, foreground, offsets=None, stream_stride=None) -> None:
         """recut_cuts_torch with cuts = [(reduce, quota, shift), ...] and a rectangle per frame: rois, a cuda int32 / uint32 tensor
@@ -654,36 +531,18 @@ class Recutter:
         Everything else as recut_cuts_torch; the workspace is cached per stream, apart from the other calls'."""
         import torch
         n, Q = int(lens.shape[0]), len(cuts)
-        if offsets is None and stream_stride is None:
-            if data.dim() != 2:
-                raise ValueError("a 1-D blob needs offsets or stream_stride")
-            stream_stride = data.stride(0)
-        for name, t, dt in (("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8),
-                            ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32), ("kept", kept, torch.int32),
-                            ("foreground", foreground, torch.int32)) + \
-                ((("offsets", offsets, torch.int64),) if offsets is not None else ()):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
-                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("out", out, torch.uint8), ("sizes", sizes, torch.int64),
+                      ("rcs", rcs, torch.int32), ("kept", kept, torch.int32), ("foreground", foreground, torch.int32),
+                      ("offsets", offsets, torch.int64))
         if not rois.is_cuda or not rois.is_contiguous() or rois.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or \
                 tuple(rois.shape) != (n, 4):
             raise ValueError("rois: a contiguous cuda int32 / uint32 tensor (n, 4) is needed")
         if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or any(t.numel() != Q * n for t in (sizes, rcs, kept, foreground)):
             raise ValueError("out must be (Q * n, out_stride), sizes, rcs, kept and foreground Q * n entries")
-        st = torch.cuda.current_stream(data.device)
-        need = self.roi_workspace_bytes(n, data.numel(), Q)
-        work = self._roi_workspaces.get(st.cuda_stream)
-        if work is None or work.numel() < max(need, 1):
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
-            self._roi_workspaces[st.cuda_stream] = work
-        work.record_stream(st)
-        rc = self.recut_roi_device_async_ptrs(n, data.data_ptr(), data.numel(), offsets.data_ptr() if offsets is not None else None,
-                                              int(stream_stride or 0), lens.data_ptr(), rois.data_ptr(), [c[0] for c in cuts],
-                                              [c[2] for c in cuts], [c[1] for c in cuts], out.data_ptr(), out.shape[-1],
-                                              sizes.data_ptr(), rcs.data_ptr(), kept.data_ptr(), foreground.data_ptr(), work.data_ptr(),
-                                              work.numel(), st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_recut_device_roi_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
-
+        _enqueue(self.lib, "icerx_recut_device_roi_async", self._roi_workspaces, self.roi_workspace_bytes(n, data.numel(), Q), data.device,
+                 self.recut_roi_device_async_ptrs, n, data, data.numel(), offsets, stream_stride, lens, rois, [c[0] for c in cuts],
+                 [c[2] for c in cuts], [c[1] for c in cuts], out, out.shape[-1], sizes, rcs, kept, foreground)
 
     # ---- refinement increments: the difference and the union of two stored streams (icerx_combine_device_async) ----
     def combine_workspace_bytes(self, n: int, data_bytes: int) -> int:
@@ -715,36 +574,16 @@ class Recutter:
         row.  The workspace is cached per stream, apart from the other calls'."""
         import torch
         n = int(lens_a.shape[0])
-        if stream_stride is None:
-            if offsets_a is None or offsets_b is None:
-                if data.dim() < 2:
-                    raise ValueError("a 1-D blob needs offsets or stream_stride")
-                stream_stride = data.stride(-2)
-            else:
-                stream_stride = 0
-        for name, t, dt in (("data", data, torch.uint8), ("lens_a", lens_a, torch.int64), ("lens_b", lens_b, torch.int64),
-                            ("out", out, torch.uint8), ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32),
-                            ("counts", counts, torch.int32)) + \
-                tuple((nm, t, torch.int64) for nm, t in (("offsets_a", offsets_a), ("offsets_b", offsets_b)) if t is not None):
-            if not t.is_cuda or not t.is_contiguous() or t.dtype != dt:
-                raise ValueError(f"{name}: a contiguous cuda {dt} tensor is needed")
+        stream_stride = _stream_stride(data, stream_stride, (offsets_a, offsets_b), any_rows=True)
+        _need_tensors(("data", data, torch.uint8), ("lens_a", lens_a, torch.int64), ("lens_b", lens_b, torch.int64), ("out", out, torch.uint8),
+                      ("sizes", sizes, torch.int64), ("rcs", rcs, torch.int32), ("counts", counts, torch.int32),
+                      ("offsets_a", offsets_a, torch.int64), ("offsets_b", offsets_b, torch.int64))
         if out.dim() != 2 or out.shape[0] != n or any(t.numel() != n for t in (lens_b, sizes, rcs)) or counts.numel() != 2 * n or \
                 any(t is not None and t.numel() != n for t in (offsets_a, offsets_b)):
             raise ValueError("out must be (n, out_stride), lens, offsets, sizes and rcs n entries, counts 2 n")
-        st = torch.cuda.current_stream(data.device)
-        need = self.combine_workspace_bytes(n, data.numel())
-        work = self._combine_workspaces.get(st.cuda_stream)
-        if work is None or work.numel() < max(need, 1):
-            work = torch.empty(max(need, 1), dtype=torch.uint8, device=data.device)
-            self._combine_workspaces[st.cuda_stream] = work
-        work.record_stream(st)
-        rc = self.combine_device_async_ptrs(n, op, data.data_ptr(), data.numel(), offsets_a.data_ptr() if offsets_a is not None else None,
-                                            int(base_a), lens_a.data_ptr(), offsets_b.data_ptr() if offsets_b is not None else None,
-                                            int(base_b), lens_b.data_ptr(), int(stream_stride), out.data_ptr(), out.shape[-1],
-                                            sizes.data_ptr(), rcs.data_ptr(), counts.data_ptr(), work.data_ptr(), work.numel(),
-                                            st.cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"icerx_combine_device_async: {rc} {self.lib.icerx_decoder_last_error().decode()}")
+        _enqueue(self.lib, "icerx_combine_device_async", self._combine_workspaces, self.combine_workspace_bytes(n, data.numel()), data.device,
+                 self.combine_device_async_ptrs, n, op, data, data.numel(), offsets_a, int(base_a), lens_a, offsets_b, int(base_b), lens_b,
+                 stream_stride, out, out.shape[-1], sizes, rcs, counts)
 
     def combine(self, streams_a, streams_b, op):
         """bytes in, bytes out: res[f] = (rc, stream, packets written, of them from A) of streams_a[f] and streams_b[f] under `op`
@@ -752,23 +591,14 @@ class Recutter:
         import torch
         if len(streams_a) != len(streams_b):
             raise ValueError("one stream of each operand per frame")
-        dev = torch.device("cuda", torch.cuda.current_device())
         n = len(streams_a)
-        both = list(streams_a) + list(streams_b)
-        lens = [len(s) for s in both]
-        blob = np.frombuffer(b"".join(both), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
-        offs = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)).to(dev)
-        lens = torch.tensor(lens, dtype=torch.int64, device=dev)
-        stride = max(max(len(a) + len(b) for a, b in zip(streams_a, streams_b)), 1)
-        out = torch.zeros((n, stride), dtype=torch.uint8, device=dev)
-        sizes = torch.zeros(n, dtype=torch.int64, device=dev)
-        rcs = torch.zeros(n, dtype=torch.int32, device=dev)
-        counts = torch.zeros((n, 2), dtype=torch.int32, device=dev)
-        self.combine_torch(torch.from_numpy(blob).to(dev), op, lens[:n].contiguous(), lens[n:].contiguous(), out, sizes, rcs, counts,
-                           offsets_a=offs[:n].contiguous(), offsets_b=offs[n:].contiguous())
-        torch.cuda.current_stream(dev).synchronize()
-        out, sizes, rcs, counts = out.cpu().numpy(), sizes.cpu().numpy(), rcs.cpu().numpy(), counts.cpu().numpy()
-        return [(int(rcs[f]), out[f, : int(sizes[f])].tobytes(), int(counts[f, 0]), int(counts[f, 1])) for f in range(n)]
+        counts = torch.zeros((n, 2), dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+        rows = _bytes_through(list(streams_a) + list(streams_b), n, max(max(len(a) + len(b) for a, b in zip(streams_a, streams_b)), 1),
+                              lambda blob, lens, offs, out, sizes, rcs:
+                              self.combine_torch(blob, op, lens[:n].contiguous(), lens[n:].contiguous(), out, sizes, rcs, counts,
+                                                 offsets_a=offs[:n].contiguous(), offsets_b=offs[n:].contiguous()))
+        counts = counts.cpu().numpy()
+        return [row + (int(counts[f, 0]), int(counts[f, 1])) for f, row in enumerate(rows)]
 
 
 # ---- standalone wavelet transform, inverse (include/icer_hip_dec.h; the forward is in api.py) -------------------------

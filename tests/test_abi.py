@@ -18,6 +18,73 @@ def _declared_functions(header="icer_hip.h"):
     return sorted(set(re.findall(r"\b(icerx?_[a-z0-9_]+)\s*\(", src)))
 
 
+def _prototypes(header):
+    """name -> (return type, [parameter declarations]) of every function the header declares"""
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(icerx?_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [p.strip() for p in params.split(",")]
+        protos[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return protos
+
+
+_INTEGERS = (C.c_int, C.c_uint, C.c_int8, C.c_uint8, C.c_int16, C.c_uint16, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64)
+_C_WIDTH = {"int": 4, "unsigned": 4, "enum icer_filter_types": 4, "uint8_t": 1, "uint32_t": 4, "int32_t": 4}
+_RETURNS = {"int": C.c_int, "void": None, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "const char *": C.c_char_p}
+
+
+def _is_pointer(ctype):
+    return isinstance(ctype, type) and issubclass(ctype, (C._Pointer, C.c_void_p, C.c_char_p, np.ctypeslib._ndptr))
+
+
+def _parameter_fits(decl, ctype):
+    """one C parameter declaration against the ctype the table gives it"""
+    if "*" in decl or "[" in decl:
+        return _is_pointer(ctype)
+    c_type = " ".join(w for w in re.sub(r"\w+$", "", decl).split() if w != "const")       # (without the parameter's name)
+    exact = {"size_t": C.c_size_t, "uint64_t": C.c_uint64, "double": C.c_double}
+    if c_type in exact:
+        return ctype is exact[c_type]
+    return ctype in _INTEGERS and C.sizeof(ctype) <= _C_WIDTH[c_type]
+
+
+def _table_problems(header, table):
+    problems = []
+    for name, (ret, params) in _prototypes(header).items():
+        if name not in table:
+            problems.append(f"{name}: no entry")
+            continue
+        restype, argtypes = table[name]
+        if restype is not _RETURNS[ret]:
+            problems.append(f"{name}: returns {ret}, declared {restype}")
+        if len(argtypes) != len(params):
+            problems.append(f"{name}: {len(params)} parameters, {len(argtypes)} declared")
+            continue
+        problems += [f"{name}: parameter {k} `{decl}` declared {ctype}" for k, (decl, ctype) in enumerate(zip(params, argtypes))
+                     if not _parameter_fits(decl, ctype)]
+    return problems
+
+
+@pytest.mark.parametrize("header,table,count", [("icer_hip.h", "ENCODER", 48), ("icer_hip_dec.h", "DECODER", 46)])
+def test_declaration_table_matches_the_header(header, table, count):
+    """icer_compression_amd/_abi.py against the prototypes: an entry for every function, the parameter count, and per parameter and
+    return the kind and width of its C type (an undeclared or narrower one is passed or returned as a 32-bit int, silently)"""
+    from icer_compression_amd import _abi
+    table = getattr(_abi, table)
+    protos = _prototypes(header)
+    assert sorted(protos) == _declared_functions(header) and len(protos) == count
+    assert _table_problems(header, table) == []
+    # the check itself: a deleted entry and a size_t declared c_int are both found
+    name = next(n for n, (_, params) in protos.items() if any(p.startswith("size_t ") for p in params))
+    k = next(k for k, p in enumerate(protos[name][1]) if p.startswith("size_t "))
+    narrowed = list(table[name][1])
+    narrowed[k] = C.c_int
+    assert _table_problems(header, {**table, name: (table[name][0], narrowed)}) == [f"{name}: parameter {k} `{protos[name][1][k]}` declared {C.c_int}"]
+    assert _table_problems(header, {n: e for n, e in table.items() if n != name}) == [f"{name}: no entry"]
+
+
 def test_library_exports_every_declared_symbol():
     lib = api.load_library()
     names = _declared_functions()

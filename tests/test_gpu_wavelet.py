@@ -235,7 +235,6 @@ def test_device_call_argument_checks():
     with pytest.raises(ValueError):
         decoder.wavelet_inverse_torch(torch.zeros((3, 0, 8), dtype=torch.int16, device="cuda"), 1, 0)
     lib = api.load_library()
-    lib.icerx_wavelet_forward_device.restype = C.c_int
     d = torch.zeros((8, 8), dtype=torch.int16, device="cuda")
     rc = lib.icerx_wavelet_forward_device(C.c_void_p(d.data_ptr()), C.c_int(70000), C.c_size_t(8), C.c_size_t(8), C.c_size_t(0), C.c_int(1),
                                           C.c_int(0), C.c_int(16), C.c_void_p(d.data_ptr()), C.c_void_p(d.data_ptr()), None)

@@ -251,8 +251,6 @@ def test_reduced_argument_errors(mock_lib):
         for reduce in range(stages):
             assert mock_lib.icerx_decoder_create_reduced(C.byref(h), -1, 3, stages, 0, 4, 8, reduce) == 0
             assert mock_lib.icerx_decoder_reduce(h) == reduce
-            mock_lib.icerx_decoder_destroy.argtypes = [C.c_void_p]
-            mock_lib.icerx_decoder_destroy.restype = None
             mock_lib.icerx_decoder_destroy(h)
     from icer_compression_amd import decoder
     with pytest.raises(RuntimeError):

@@ -29,16 +29,11 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(1)
     dt = torch.int16 if a.bits == 16 else torch.int8
     src = torch.randint(0, 1 << (a.bits - 4), (1, a.size, a.size), device="cuda", generator=g, dtype=torch.int32).to(dt)
-    import ctypes as C
     enc, dec = api.load_library(), decoder.load_library()
-    enc.icerx_wavelet_workspace_bytes.restype = C.c_size_t
-    enc.icerx_wavelet_workspace_bytes.argtypes = [C.c_size_t, C.c_size_t, C.c_int, C.c_int]
     # the workspace, the result codes and the argument conversion are set up once, outside the timed window
     ws = torch.empty(int(enc.icerx_wavelet_workspace_bytes(a.size, a.size, 1, a.bits)), dtype=torch.uint8, device="cuda")
     rcs = torch.zeros(1, dtype=torch.int32, device="cuda")
     for name, fn in (("forward", enc.icerx_wavelet_forward_device), ("inverse", dec.icerx_wavelet_inverse_device)):
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         for filt in range(7):
             plane = src.clone()
             st = torch.cuda.current_stream().cuda_stream
