@@ -5,6 +5,8 @@
 //   chains of all streams (one wavefront per chain; one thread per chain with ICER_DEC_WAVE=0) | if the decoder asks
 //   for it, truncated coefficients part-way into their interval (decoder_recon.hpp) | sign-magnitude removal + LL mean | inverse DWT, one level at a time, one thread per line, all frames of a geometry per launch
 //   | clamp, narrow, copy back.
+// decode_batch runs that as five stages over one BatchRun: batch_packets, batch_plans, batch_chains, batch_samples, batch_results.
+// Which kernel takes a chain, in what order and with how much LDS: decoder_route.hpp (route_batch_chains; shared with the async decode).
 // icerx_decode_device_async runs the same chain kernels with everything planned on the device (decoder_async.hpp).
 // First version: correctness before speed (HISTORY.md 6b (summary: DESIGN.md 8)); every loop is bounded by the stream / image size and no
 // kernel waits on another thread.
@@ -49,6 +51,7 @@
 #include "decoder_planes.hpp"
 #include "decoder_core.hpp"
 #include "decoder_plan.hpp"
+#include "decoder_route.hpp"
 
 using namespace icer;
 
@@ -302,8 +305,7 @@ struct icerx_decoder {
     int is_gfx950 = -1;                // (-1: not asked yet)
     size_t planes_lds_fallback = 0;    // ... or, refused the hardware's figure, this much (what the runtime reports)
     bool planes_lds_refused = false;   // ... or the runtime refused: chains that need more than 48 KiB go to the lane-per-plane kernel from then on
-    // the lane-per-plane kernel is launched once per size class of row ring, side by side (decode_batch)
-    static constexpr int kRingClasses = 4;
+    // the lane-per-plane kernel is launched once per size class of row ring, side by side (batch_chains; decoder_route.hpp)
     hipStream_t side[kRingClasses] = {};
     bool side_ok = false;
     // icerx_decode_device_async: the events that fork its side-stream work from the caller's stream and join it back, and
@@ -375,65 +377,72 @@ size_t resolve_planes_lds(icerx_decoder *d)
 #endif
 }
 
-// n streams: stream k = bytes [offsets[k], offsets[k] + lens[k]) of `data` (host memory, or device memory when
-// data_on_device).  Results: rcs[k], ws[k] / hs[k] (in: the values kept when stream k holds no valid packet).  Frame k's
-// channel c goes to host_out[k * channels + c] (host pointers, >= frame_stride samples each) or, when host_out is null, to
-// dev_out + (k * channels + c) * frame_stride samples (device memory; uint16 or uint8 samples by sample_bits).
-// Display calls (host_out and dev_out null): frame k's 8-bit image (decoder_display.hpp) goes to disp_host[k] (host pointers,
-// channels * frame_stride bytes each) or, when disp_host is null, to disp_dev + k * channels * frame_stride bytes.
-int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_device, const size_t *offsets, const size_t *lens,
-                 void *const *host_out, void *dev_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs,
-                 uint8_t *const *disp_host = nullptr, uint8_t *disp_dev = nullptr)
+// the side streams of a decoder, made by the first call that needs them (none is kept half-made: the next call tries again)
+int ensure_side_streams(icerx_decoder *d)
 {
-    g_error.clear();
-    if (!d || n < 0 || (n && (!offsets || !lens || !rcs || !ws || !hs)) || (!host_out && !dev_out && !disp_host && !disp_dev && n)) return ICER_INVALID_INPUT;
-    if (n == 0) return ICER_RESULT_OK;
+#ifndef ICER_HOST_MOCK
+    if (d->side_ok) return ICER_RESULT_OK;
+    bool made = true;
+    for (hipStream_t &st : d->side) made = made && create_side_stream(&st) == hipSuccess;
+    if (!made) {
+        for (hipStream_t &st : d->side) { if (st) (void)hipStreamDestroy(st); st = nullptr; }
+        (void)hipGetLastError();
+        return fail("the decoder could not create its side streams");
+    }
+    d->side_ok = true;
+#endif
+    (void)d;
+    return ICER_RESULT_OK;
+}
+
+// ------------------------------------------------------------------------------------------ synchronous batch decode
+// Where decode_batch leaves its results, `p` by kind.  kHostPlanes: void *const *, frame k's channel c goes to p[k * channels + c]
+// (host pointers, >= frame_stride samples each); kDevPlanes: device memory, to p + (k * channels + c) * frame_stride samples
+// (uint16 or uint8 samples by sample_bits).  Display calls, frame k's 8-bit image (decoder_display.hpp) -- kHostDisplay:
+// uint8_t *const *, to p[k] (host pointers, channels * frame_stride bytes each); kDevDisplay: device memory, to
+// p + k * channels * frame_stride bytes.
+struct BatchOut {
+    enum Kind { kHostPlanes, kDevPlanes, kHostDisplay, kDevDisplay } kind;
+    const void *p;
+};
+
+// one call of decode_batch: what its stages (batch_packets .. batch_results, in this order) hand to one another
+struct BatchRun {
+    icerx_decoder *d;
+    int n;
+    size_t frame_stride;
+    PlaneBits pb;
+    std::vector<FrameInfo> frames;
+    std::vector<DecodePlan> plans;
+    std::vector<ChainDesc> chains;       // from batch_chains on: in launch order (route_batch_chains), as uploaded to d->chains
+    const uint8_t *d_data;
+    FrameInfo *d_frames;
+    uint16_t *d_planes;
+    size_t planes_total() const { return (size_t)n * d->channels * frame_stride; }
+    dim3 grid_all() const { return dim3((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * d->channels)); }
+};
+
+// 1. packets: the streams on the device, their header candidates with checked payloads, in stream and offset order
+int batch_packets(BatchRun &r, const uint8_t *data, bool data_on_device, size_t total_len, size_t max_len, std::vector<PacketCandidate> &cands)
+{
+    icerx_decoder *d = r.d;
     int rc = ICER_RESULT_OK;
-    const int channels = d->channels, bits = d->bits, stages = d->stages;
-    const int nplanes = bits == 8 ? kPlanes8 : kPlanes, sign_bit = bits == 8 ? 7 : 15;
-    const int recon = d->recon;
-    size_t total_len = 0, max_len = 0;
-    for (int k = 0; k < n; k++) {
-        if (lens[k] && !data) return ICER_INVALID_INPUT;
-        total_len = std::max(total_len, offsets[k] + lens[k]);
-        max_len = std::max(max_len, lens[k]);
-    }
-    if (total_len >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", total_len);
-    const size_t planes_total = (size_t)n * channels * frame_stride;
-    if (frame_stride > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", frame_stride);
-
-    std::vector<FrameInfo> frames((size_t)n);
-    std::vector<PacketCandidate> cands;
-    std::vector<DecodePlan> plans((size_t)n);
-    std::vector<ChainDesc> chains;
-    const uint8_t *d_data = nullptr;
-    uint16_t *d_planes = nullptr;
-    uint8_t *d_out8 = nullptr;
-    FrameInfo *d_frames = nullptr;
-
-    for (int k = 0; k < n; k++) {
-        memset(&frames[k], 0, sizeof(FrameInfo));
-        frames[k].stream_off = (uint32_t)offsets[k];
-        frames[k].stream_len = (uint32_t)lens[k];
-    }
-    HIP_TRY(ensure(d->frames, sizeof(FrameInfo) * n));
-    d_frames = (FrameInfo *)d->frames.p;
-    HIP_TRY(hipMemcpy(d_frames, frames.data(), sizeof(FrameInfo) * n, hipMemcpyHostToDevice));
-
-    // 1. packets
+    HIP_TRY(ensure(d->frames, sizeof(FrameInfo) * r.n));
+    r.d_frames = (FrameInfo *)d->frames.p;
+    HIP_TRY(hipMemcpy(r.d_frames, r.frames.data(), sizeof(FrameInfo) * r.n, hipMemcpyHostToDevice));
     if (total_len) {
-        if (data_on_device) d_data = data;
+        if (data_on_device) r.d_data = data;
         else {
             HIP_TRY(ensure(d->data, total_len));
             HIP_TRY(hipMemcpy(d->data.p, data, total_len, hipMemcpyHostToDevice));
-            d_data = (const uint8_t *)d->data.p;
+            r.d_data = (const uint8_t *)d->data.p;
         }
         HIP_TRY(ensure(d->count, sizeof(uint32_t)));
         uint32_t cap = (uint32_t)(total_len / 64u) + 1024u, count = 0;
         for (int attempt = 0; attempt < 2 && max_len; attempt++) {
             HIP_TRY(ensure(d->cands, sizeof(PacketCandidate) * cap));
             HIP_TRY(hipMemset(d->count.p, 0, sizeof(uint32_t)));
-            ICER_LAUNCH(count_headers_kernel, dim3((unsigned)((max_len + 255u) / 256u), (unsigned)n), 256, 0, d_data, d_frames,
+            ICER_LAUNCH(count_headers_kernel, dim3((unsigned)((max_len + 255u) / 256u), (unsigned)r.n), 256, 0, r.d_data, r.d_frames,
                         (const uint32_t *)d->crc.p, (PacketCandidate *)d->cands.p, cap, (uint32_t *)d->count.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(&count, d->count.p, sizeof count, hipMemcpyDeviceToHost));
@@ -441,8 +450,7 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
             cap = count;                                    // (more header look-alikes than expected: once more, all of them)
         }
         if (count) {
-            ICER_LAUNCH(check_payloads_kernel, count, 64, 0, d_data, d_frames, (const uint32_t *)d->crc.p,
-                        (PacketCandidate *)d->cands.p, count);
+            ICER_LAUNCH(check_payloads_kernel, count, 64, 0, r.d_data, r.d_frames, (const uint32_t *)d->crc.p, (PacketCandidate *)d->cands.p, count);
             HIP_TRY(hipGetLastError());
             cands.resize(count);
             HIP_TRY(hipMemcpy(cands.data(), d->cands.p, sizeof(PacketCandidate) * count, hipMemcpyDeviceToHost));
@@ -452,244 +460,231 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
             });
         }
     }
+done:
+    return rc;
+}
 
-    // 2. plans
-    {
-        size_t at = 0;
-        std::vector<PacketCandidate> mine;
-        for (int k = 0; k < n; k++) {
-            mine.clear();
-            while (at < cands.size() && cands[at].frame == (uint32_t)k) mine.push_back(cands[at++]);
-            DecodePlan &pl = plans[k];
-            plan_decode(&pl, mine, channels, stages, d->segments, bits, ws[k], hs[k], frame_stride, d->reduce);
-            ws[k] = pl.w; hs[k] = pl.h; rcs[k] = pl.rc;
-            const bool runs = !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
-            frames[k].w = runs ? (uint32_t)pl.w : 0u;
-            frames[k].h = runs ? (uint32_t)pl.h : 0u;
-            frames[k].ll_w = (uint32_t)dim_low(pl.w, stages); frames[k].ll_h = (uint32_t)dim_low(pl.h, stages);
-            for (int c = 0; c < 3; c++) frames[k].mean[c] = pl.mean[c];
-            frames[k].transform = (runs && pl.transform) ? 1u : 0u;
-            if (!runs) continue;
-            for (ChainDesc c : pl.chains) { c.frame = (uint32_t)k; chains.push_back(c); }
-        }
+// 2. plans: per stream the packet walk (plan_decode) -- its results, its FrameInfo (uploaded again) and its chains
+int batch_plans(BatchRun &r, const std::vector<PacketCandidate> &cands, int *rcs, size_t *ws, size_t *hs)
+{
+    const icerx_decoder *d = r.d;
+    int rc = ICER_RESULT_OK;
+    size_t at = 0;
+    std::vector<PacketCandidate> mine;
+    for (int k = 0; k < r.n; k++) {
+        mine.clear();
+        while (at < cands.size() && cands[at].frame == (uint32_t)k) mine.push_back(cands[at++]);
+        DecodePlan &pl = r.plans[k];
+        FrameInfo &f = r.frames[k];
+        plan_decode(&pl, mine, d->channels, d->stages, d->segments, d->bits, ws[k], hs[k], r.frame_stride, d->reduce);
+        ws[k] = pl.w; hs[k] = pl.h; rcs[k] = pl.rc;
+        const bool runs = !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
+        f.w = runs ? (uint32_t)pl.w : 0u;
+        f.h = runs ? (uint32_t)pl.h : 0u;
+        f.ll_w = (uint32_t)dim_low(pl.w, d->stages); f.ll_h = (uint32_t)dim_low(pl.h, d->stages);
+        for (int c = 0; c < 3; c++) f.mean[c] = pl.mean[c];
+        f.transform = (runs && pl.transform) ? 1u : 0u;
+        if (!runs) continue;
+        for (ChainDesc c : pl.chains) { c.frame = (uint32_t)k; r.chains.push_back(c); }
     }
-    HIP_TRY(hipMemcpy(d_frames, frames.data(), sizeof(FrameInfo) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.d_frames, r.frames.data(), sizeof(FrameInfo) * r.n, hipMemcpyHostToDevice));
+done:
+    return rc;
+}
 
-    // 3. bit planes: into the caller's device buffer when that holds uint16 samples, else into a work buffer
-    if (planes_total == 0) goto done;
-    if (dev_out && !host_out && bits == 16) d_planes = (uint16_t *)dev_out;
-    else { HIP_TRY(ensure(d->work, sizeof(uint16_t) * planes_total)); d_planes = (uint16_t *)d->work.p; }
+// 3. bit planes: into the caller's device buffer when that holds uint16 samples, else into a work buffer; the chains routed
+// (decoder_route.hpp), uploaded and decoded -- the wave-per-plane share on the null stream, the ring classes side by side with it
+int batch_chains(BatchRun &r, const BatchOut &out)
+{
+    icerx_decoder *d = r.d;
+    const int channels = d->channels, nplanes = r.pb.nplanes, sign_bit = r.pb.sign_bit;
+    int rc = ICER_RESULT_OK;
+    if (out.kind == BatchOut::kDevPlanes && d->bits == 16) r.d_planes = (uint16_t *)out.p;
+    else { HIP_TRY(ensure(d->work, sizeof(uint16_t) * r.planes_total())); r.d_planes = (uint16_t *)d->work.p; }
     // (only the w * h samples of a frame are defined results; the rest of its slot is scratch)
-    HIP_TRY(hipMemset(d_planes, 0, sizeof(uint16_t) * planes_total));
-    if (!chains.empty()) {
-        // Which kernel decodes a chain (ICER_DEC_WAVE: 0 = one thread per chain, 1 = one wavefront per chain with a lane per
-        // bit plane, anything else / unset = one wavefront per bit plane wherever it applies):
-        //   wave-per-plane   chains whose packets all take the fast entropy path (ChainDesc::fast) and whose row ring fits LDS
-        //   the rest         the lane-per-plane kernel if ITS ring fits, else one thread per chain
-        // Unset, the choice goes by load.  A wave per plane is the faster DECISION (303 against 634 ms for the 160 chains of
-        // the 4096 x 4096 headline stream), but a compute unit's throughput with it saturates near ONE long chain (what the
-        // waves of several chains share is the compute unit's scalar unit: 0.6-0.75 scalar instructions per cycle at 8-16
-        // streams, profiles/r04_logs/r04_l_planes_sq_counters.log; the wait loops are not it, r04_m), while the lane-per-plane
-        // kernel keeps seven long chains per compute unit going (LDS for their row rings), each at half the speed.  With the
-        // chains in longest-first order (below; profiles/r04_logs/r04_k_*.json, r04_m_*.json), streams per call -> Mpix/s:
-        //   wave per plane   4: 220   8: 437   16: 525-586   32: 537   64: 519
-        //   lane per plane   4: 107            16: 435       32: 922   64: 885-921   128: 1036
-        // -- the cross-over lies near 20 streams = 12 chains per compute unit (24 streams by this rule: 686).  ICER_DEC_WAVE=2
-        // pins the wave-per-plane kernel.
-        const char *mode = getenv("ICER_DEC_WAVE");
-        size_t n_eligible = 0;
-        for (const ChainDesc &c : chains) n_eligible += c.fast ? 1u : 0u;
-        const bool by_load = !mode || !mode[0];
-        const bool want_planes = !(mode && (mode[0] == '0' || mode[0] == '1')) && d->tables.lut_ok != 0u &&
-                                 (!by_load || n_eligible <= 12u * (size_t)d->n_cus);
-        size_t planes_lds = 0;
+    HIP_TRY(hipMemset(r.d_planes, 0, sizeof(uint16_t) * r.planes_total()));
+    if (!r.chains.empty()) {
+        const int mode = dec_wave_mode();
+        uint32_t n_eligible = 0;
+        for (const ChainDesc &c : r.chains) n_eligible += c.fast ? 1u : 0u;
+        const bool want_planes = dwant_planes(mode, d->tables.lut_ok, n_eligible, (uint32_t)d->n_cus);
         const size_t planes_lds_limit = resolve_planes_lds(d);
-        std::stable_partition(chains.begin(), chains.end(), [&](const ChainDesc &c) {
-            return want_planes && c.fast && frames[c.frame].stream_len >= 4u && pw_lds_bytes(c.w, nplanes) <= planes_lds_limit; });
-        uint32_t n_fast = 0;
-        for (const ChainDesc &c : chains) {
-            if (!(want_planes && c.fast && frames[c.frame].stream_len >= 4u && pw_lds_bytes(c.w, nplanes) <= planes_lds_limit)) break;
-            planes_lds = std::max(planes_lds, pw_lds_bytes(c.w, nplanes));
-            n_fast++;
-        }
-        const uint32_t nc = (uint32_t)chains.size();
-        // Longest chains first within either kernel's share (a chain's time goes with its samples): the level-1 chains of
-        // every stream start at once, one or two per compute unit, and the short ones fill the gaps -- in stream order the
-        // long chains of the later streams of a batch started when those of the first were half-way.
-        auto longer = [](const ChainDesc &a, const ChainDesc &b) { return (uint32_t)a.w * a.h > (uint32_t)b.w * b.h; };
-        std::stable_sort(chains.begin(), chains.begin() + n_fast, longer);
-        std::stable_sort(chains.begin() + n_fast, chains.end(), longer);
-        // The lane-per-plane kernel's share by size class of row ring (a launch reserves the LDS of its widest chain for every
-        // workgroup, and LDS is what bounds the chains a compute unit holds: 7 of the headline stream's level-1 chains, but 14
-        // of level 2 and 28 of level 3): class k = rings of at most limit >> k bytes, widest class first, each class a launch
-        // of its own on a stream of its own, all of them side by side.
-        uint32_t class_end[icerx_decoder::kRingClasses];
-        {
-            size_t widest = 2;
-            for (uint32_t i = n_fast; i < nc; i++) widest = std::max(widest, ring_elems_for(chains[i].w, nplanes));
-            auto cls = [&](const ChainDesc &c) {
-                const size_t e = ring_elems_for(c.w, nplanes);
-                int k = 0;
-                while (k + 1 < icerx_decoder::kRingClasses && e * 2u <= (widest >> k)) k++;
-                return k;
-            };
-            std::stable_sort(chains.begin() + n_fast, chains.end(), [&](const ChainDesc &a, const ChainDesc &b) { return cls(a) < cls(b); });
-            uint32_t at = n_fast;
-            for (int k = 0; k < icerx_decoder::kRingClasses; k++) {
-                while (at < nc && cls(chains[at]) == k) at++;
-                class_end[k] = at;
-            }
-        }
+        const BatchRoute route = route_batch_chains(r.chains, [&](uint32_t f) { return r.frames[f].stream_len; }, want_planes, planes_lds_limit, nplanes);
+        const uint32_t nc = (uint32_t)r.chains.size(), n_fast = route.n_fast;
+        const DecoderTables *tables = (const DecoderTables *)d->dtables.p;
         HIP_TRY(ensure(d->chains, sizeof(ChainDesc) * nc));
-        HIP_TRY(hipMemcpy(d->chains.p, chains.data(), sizeof(ChainDesc) * nc, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d->chains.p, r.chains.data(), sizeof(ChainDesc) * nc, hipMemcpyHostToDevice));
+        const ChainDesc *d_chains = (const ChainDesc *)d->chains.p;
         if (n_fast) {
             HIP_TRY(ensure(d->err, sizeof(uint32_t)));
             HIP_TRY(hipMemset(d->err.p, 0, sizeof(uint32_t)));
-            ICER_LAUNCH_PLANES(decode_chains_planes_kernel, n_fast, planes_lds, d_planes, frame_stride, channels, (const ChainDesc *)d->chains.p,
-                               d_data, d_frames, (const DecoderTables *)d->dtables.p, nplanes, sign_bit, (uint32_t *)d->err.p);
+            ICER_LAUNCH_PLANES(decode_chains_planes_kernel, n_fast, route.planes_lds, r.d_planes, r.frame_stride, channels, d_chains, r.d_data,
+                               r.d_frames, tables, nplanes, sign_bit, (uint32_t *)d->err.p);
             HIP_TRY(hipGetLastError());
         }
         if (n_fast < nc) {
-            const ChainDesc *rest = (const ChainDesc *)d->chains.p + n_fast;
-            const uint32_t nr = nc - n_fast;
             // the planes of a segment side by side (one wavefront per chain) if the chain's row ring fits LDS
-            size_t ring_elems = 2;
-            for (uint32_t i = n_fast; i < nc; i++) ring_elems = std::max(ring_elems, ring_elems_for(chains[i].w, nplanes));
-            const size_t ring_bytes = ring_elems * sizeof(uint16_t) + kStateBytes;
+            const size_t ring_bytes = route.rest_ring_elems * sizeof(uint16_t) + kStateBytes;
             // (the kernel's static DecoderTables block counts against the same 64 KiB a launch gets without asking)
-            if (!(mode && mode[0] == '0') && ring_bytes + sizeof(DecoderTables) + 256u <= 65536u) {
-#ifndef ICER_HOST_MOCK
-                if (!d->side_ok) {
-                    bool made = true;
-                    for (hipStream_t &st : d->side) made = made && create_side_stream(&st) == hipSuccess;
-                    if (!made) {                                    // (none is kept half-made: the next call tries again)
-                        for (hipStream_t &st : d->side) { if (st) (void)hipStreamDestroy(st); st = nullptr; }
-                        (void)hipGetLastError();
-                        rc = fail("the decoder could not create its side streams");
-                        goto done;
-                    }
-                    d->side_ok = true;
-                }
-#endif
+            if (mode != 0 && ring_bytes + sizeof(DecoderTables) + 256u <= 65536u) {
+                if ((rc = ensure_side_streams(d)) != ICER_RESULT_OK) goto done;
                 // (everything the null stream did so far is complete: the upload of `chains` above was a blocking copy)
                 uint32_t from = n_fast;
-                for (int k = 0; k < icerx_decoder::kRingClasses; k++) {
-                    const uint32_t to = class_end[k];
-                    if (to == from) continue;
-                    size_t elems = 2;
-                    for (uint32_t i = from; i < to; i++) elems = std::max(elems, ring_elems_for(chains[i].w, nplanes));
-                    ICER_LAUNCH_WAVE_ON(d->side[k], decode_chains_wave_kernel, to - from, elems * sizeof(uint16_t) + kStateBytes, d_planes, frame_stride, channels,
-                                        (const ChainDesc *)d->chains.p + from, d_data, d_frames, (const DecoderTables *)d->dtables.p, nplanes, sign_bit);
+                for (int k = 0; k < kRingClasses; from = route.class_end[k++]) {
+                    if (route.class_end[k] == from) continue;
+                    ICER_LAUNCH_WAVE_ON(d->side[k], decode_chains_wave_kernel, route.class_end[k] - from, route.class_elems[k] * sizeof(uint16_t) + kStateBytes,
+                                        r.d_planes, r.frame_stride, channels, d_chains + from, r.d_data, r.d_frames, tables, nplanes, sign_bit);
                     HIP_TRY(hipGetLastError());
-                    from = to;
                 }
 #ifndef ICER_HOST_MOCK
                 for (hipStream_t st : d->side) HIP_TRY(hipStreamSynchronize(st));
 #endif
             } else {
-                ICER_LAUNCH(decode_chains_kernel, (nr + 63u) / 64u, 64, plane_block_bytes(64u), d_planes, frame_stride, channels, rest,
-                            nr, d_data, d_frames, (const DecoderTables *)d->dtables.p, nplanes, sign_bit);
+                ICER_LAUNCH(decode_chains_kernel, (nc - n_fast + 63u) / 64u, 64, plane_block_bytes(64u), r.d_planes, r.frame_stride, channels,
+                            d_chains + n_fast, nc - n_fast, r.d_data, r.d_frames, tables, nplanes, sign_bit);
             }
             HIP_TRY(hipGetLastError());
         }
         if (n_fast) {
             uint32_t err = 0;
             HIP_TRY(hipMemcpy(&err, d->err.p, sizeof err, hipMemcpyDeviceToHost));
-            if (err) { rc = fail("a bit-plane wave of the decoder waited longer than its spin bound (internal error)"); goto done; }
+            if (err) rc = fail("a bit-plane wave of the decoder waited longer than its spin bound (internal error)");
         }
-    }
-
-    // 4. samples
-    {
-        const dim3 grid_all((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * channels));
-        if (recon != 0 && !chains.empty()) {                 // (the chain kernels are complete: the side streams were waited for)
-            ICER_LAUNCH(reconstruct_kernel, dim3((unsigned)chains.size(), kReconParts), kReconThreads, 0, d_planes, frame_stride, channels,
-                        (const ChainDesc *)d->chains.p, (uint32_t)chains.size(), d_frames, (uint32_t)n, nplanes, sign_bit, recon);
-            HIP_TRY(hipGetLastError());
-        }
-        ICER_LAUNCH(unsign_kernel, grid_all, 256, 0, d_planes, frame_stride, channels, d_frames, sign_bit, bits);
-        HIP_TRY(hipGetLastError());
-        // inverse DWT: the frames of one size together
-        std::vector<char> done((size_t)n, 0);
-        const FilterTaps taps = filter_taps(d->filt);
-        for (int k = 0; k < n; k++) {
-            if (done[k] || !frames[k].transform || plans[k].levels.empty()) continue;
-            std::vector<uint32_t> list, pos, tab;
-            for (int j = k; j < n; j++)
-                if (!done[j] && frames[j].transform && frames[j].w == frames[k].w && frames[j].h == frames[k].h) { list.push_back((uint32_t)j); done[j] = 1; }
-            const uint32_t W = frames[k].w;
-            std::vector<size_t> col_at, row_at;              // where each level's position tables start
-            for (const DecodeLevel &lv : plans[k].levels) {
-                col_at.push_back(tab.size());
-                pos.resize(lv.ch); interleave_positions(lv.ch, bits, pos.data()); tab.insert(tab.end(), pos.begin(), pos.end());
-                row_at.push_back(tab.size());
-                pos.resize(lv.cw); interleave_positions(lv.cw, bits, pos.data()); tab.insert(tab.end(), pos.begin(), pos.end());
-            }
-            HIP_TRY(ensure(d->tmp, sizeof(uint16_t) * planes_total));
-            HIP_TRY(ensure(d->pos, sizeof(uint32_t) * tab.size()));
-            HIP_TRY(hipMemcpy(d->pos.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice));
-            HIP_TRY(ensure(d->list, sizeof(uint32_t) * list.size()));
-            HIP_TRY(hipMemcpy(d->list.p, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice));
-            const unsigned gy = (unsigned)(list.size() * (size_t)channels);
-            const bool pairwise = taps.be == 0 && taps.am1 == 0;      // (filter A: no recurrence along a line, idwt_pairs_kernel)
-            for (size_t li = 0; li < plans[k].levels.size(); li++) {
-                const DecodeLevel &lv = plans[k].levels[li];
-                if (pairwise) {
-                    ICER_LAUNCH(idwt_pairs_kernel, dim3((lv.cw + 63u) / 64u, ((lv.ch + 1u) / 2u + 3u) / 4u, gy), dim3(256), 0, (const int16_t *)d_planes,
-                                (int16_t *)d->tmp.p, frame_stride, channels, (const uint32_t *)d->list.p, W, lv.cw, lv.ch, taps, bits,
-                                (const uint32_t *)d->pos.p + col_at[li], false);
-                    HIP_TRY(hipGetLastError());
-                    ICER_LAUNCH(idwt_pairs_kernel, dim3(((lv.cw + 1u) / 2u + 63u) / 64u, (lv.ch + 3u) / 4u, gy), dim3(256), 0, (const int16_t *)d->tmp.p,
-                                (int16_t *)d_planes, frame_stride, channels, (const uint32_t *)d->list.p, W, lv.cw, lv.ch, taps, bits,
-                                (const uint32_t *)d->pos.p + row_at[li], true);
-                    HIP_TRY(hipGetLastError());
-                    continue;
-                }
-                // columns: planes -> tmp, rows: tmp -> planes (only the level's region is touched)
-                ICER_LAUNCH(idwt_lines_kernel, dim3((lv.cw + 63u) / 64u, gy), 64, 0, (const int16_t *)d_planes, (int16_t *)d->tmp.p,
-                            frame_stride, channels, (const uint32_t *)d->list.p, W, lv.cw, lv.ch, taps, bits,
-                            (const uint32_t *)d->pos.p + col_at[li], false);
-                HIP_TRY(hipGetLastError());
-                ICER_LAUNCH(idwt_lines_kernel, dim3((lv.ch + 63u) / 64u, gy), 64, 0, (const int16_t *)d->tmp.p, (int16_t *)d_planes,
-                            frame_stride, channels, (const uint32_t *)d->list.p, W, lv.cw, lv.ch, taps, bits,
-                            (const uint32_t *)d->pos.p + row_at[li], true);
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipDeviceSynchronize());                 // (the position tables and the list are reused by the next size)
-        }
-
-        // 5. results
-        if (disp_host || disp_dev) {                         // a display call: finished and converted in one pass
-            uint8_t *d_img = disp_dev;
-            if (disp_host) { HIP_TRY(ensure(d->disp, planes_total)); d_img = (uint8_t *)d->disp.p; }
-            ICER_LAUNCH(display_finish_kernel, dim3((unsigned)(((frame_stride + 3u) / 4u + 255u) / 256u), (unsigned)n), 256, 0, d_planes,
-                        frame_stride, channels, d_frames, bits, d_img);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipDeviceSynchronize());
-            for (int k = 0; k < n && disp_host; k++) {
-                const size_t bytes = (size_t)channels * frames[k].w * frames[k].h;
-                if (bytes) HIP_TRY(hipMemcpy(disp_host[k], d_img + (size_t)k * channels * frame_stride, bytes, hipMemcpyDeviceToHost));
-            }
-            goto done;
-        }
-        if (bits == 8) {
-            if (dev_out && !host_out) d_out8 = (uint8_t *)dev_out;
-            else { HIP_TRY(ensure(d->out8, planes_total)); d_out8 = (uint8_t *)d->out8.p; }
-        }
-        ICER_LAUNCH(finish_kernel, grid_all, 256, 0, d_planes, frame_stride, channels, d_frames, d_out8);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
-        if (host_out)
-            for (int k = 0; k < n; k++) {
-                const size_t samples = (size_t)frames[k].w * frames[k].h;
-                for (int c = 0; c < channels && samples; c++) {
-                    const size_t at = ((size_t)k * channels + c) * frame_stride;
-                    if (bits == 8) HIP_TRY(hipMemcpy(host_out[k * channels + c], d_out8 + at, samples, hipMemcpyDeviceToHost));
-                    else HIP_TRY(hipMemcpy(host_out[k * channels + c], d_planes + at, sizeof(uint16_t) * samples, hipMemcpyDeviceToHost));
-                }
-            }
     }
 done:
+    return rc;
+}
+
+// 4. samples: truncated coefficients rebuilt if the decoder asks for it (decoder_recon.hpp), sign-magnitude words -> int16 with
+// the LL mean, then the inverse DWT, the frames of one size together
+int batch_samples(BatchRun &r)
+{
+    icerx_decoder *d = r.d;
+    const int n = r.n, channels = d->channels, bits = d->bits;
+    const FilterTaps taps = filter_taps(d->filt);
+    const bool pairwise = taps.be == 0 && taps.am1 == 0;      // (filter A: no recurrence along a line, idwt_pairs_kernel)
+    std::vector<char> done((size_t)n, 0);
+    int rc = ICER_RESULT_OK;
+    if (d->recon != 0 && !r.chains.empty()) {                // (the chain kernels are complete: the side streams were waited for)
+        ICER_LAUNCH(reconstruct_kernel, dim3((unsigned)r.chains.size(), kReconParts), kReconThreads, 0, r.d_planes, r.frame_stride, channels,
+                    (const ChainDesc *)d->chains.p, (uint32_t)r.chains.size(), r.d_frames, (uint32_t)n, r.pb.nplanes, r.pb.sign_bit, d->recon);
+        HIP_TRY(hipGetLastError());
+    }
+    ICER_LAUNCH(unsign_kernel, r.grid_all(), 256, 0, r.d_planes, r.frame_stride, channels, r.d_frames, r.pb.sign_bit, bits);
+    HIP_TRY(hipGetLastError());
+    for (int k = 0; k < n; k++) {
+        if (done[k] || !r.frames[k].transform || r.plans[k].levels.empty()) continue;
+        std::vector<uint32_t> list, pos, tab;
+        for (int j = k; j < n; j++)
+            if (!done[j] && r.frames[j].transform && r.frames[j].w == r.frames[k].w && r.frames[j].h == r.frames[k].h) { list.push_back((uint32_t)j); done[j] = 1; }
+        std::vector<size_t> col_at, row_at;              // where each level's position tables start
+        for (const DecodeLevel &lv : r.plans[k].levels) {
+            col_at.push_back(tab.size());
+            pos.resize(lv.ch); interleave_positions(lv.ch, bits, pos.data()); tab.insert(tab.end(), pos.begin(), pos.end());
+            row_at.push_back(tab.size());
+            pos.resize(lv.cw); interleave_positions(lv.cw, bits, pos.data()); tab.insert(tab.end(), pos.begin(), pos.end());
+        }
+        HIP_TRY(ensure(d->tmp, sizeof(uint16_t) * r.planes_total()));
+        HIP_TRY(ensure(d->pos, sizeof(uint32_t) * tab.size()));
+        HIP_TRY(hipMemcpy(d->pos.p, tab.data(), sizeof(uint32_t) * tab.size(), hipMemcpyHostToDevice));
+        HIP_TRY(ensure(d->list, sizeof(uint32_t) * list.size()));
+        HIP_TRY(hipMemcpy(d->list.p, list.data(), sizeof(uint32_t) * list.size(), hipMemcpyHostToDevice));
+        const unsigned gy = (unsigned)(list.size() * (size_t)channels);
+        // one pass of a level -- columns: planes -> tmp, rows: tmp -> planes (only the level's region is touched) -- by pairs or by lines
+        auto pass = [&](const DecodeLevel &lv, size_t tab_at, bool rows) {
+            const int16_t *src = rows ? (const int16_t *)d->tmp.p : (const int16_t *)r.d_planes;
+            int16_t *dst = rows ? (int16_t *)r.d_planes : (int16_t *)d->tmp.p;
+            const uint32_t *pos_of = (const uint32_t *)d->pos.p + tab_at;
+            if (pairwise)
+                ICER_LAUNCH(idwt_pairs_kernel, rows ? dim3(((lv.cw + 1u) / 2u + 63u) / 64u, (lv.ch + 3u) / 4u, gy) : dim3((lv.cw + 63u) / 64u, ((lv.ch + 1u) / 2u + 3u) / 4u, gy),
+                            dim3(256), 0, src, dst, r.frame_stride, channels, (const uint32_t *)d->list.p, r.frames[k].w, lv.cw, lv.ch, taps, bits, pos_of, rows);
+            else
+                ICER_LAUNCH(idwt_lines_kernel, dim3(((rows ? lv.ch : lv.cw) + 63u) / 64u, gy), 64, 0, src, dst, r.frame_stride, channels,
+                            (const uint32_t *)d->list.p, r.frames[k].w, lv.cw, lv.ch, taps, bits, pos_of, rows);
+        };
+        for (size_t li = 0; li < r.plans[k].levels.size(); li++) {
+            pass(r.plans[k].levels[li], col_at[li], false);
+            HIP_TRY(hipGetLastError());
+            pass(r.plans[k].levels[li], row_at[li], true);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipDeviceSynchronize());                 // (the position tables and the list are reused by the next size)
+    }
+done:
+    return rc;
+}
+
+// 5. results: a display call is finished and converted in one pass (display_finish_kernel), planes are clamped and narrowed
+// (finish_kernel); then the copy back of a host call
+int batch_results(BatchRun &r, const BatchOut &out)
+{
+    icerx_decoder *d = r.d;
+    const int n = r.n, channels = d->channels, bits = d->bits;
+    const bool display = out.kind == BatchOut::kHostDisplay || out.kind == BatchOut::kDevDisplay, to_host = out.kind == BatchOut::kHostPlanes || out.kind == BatchOut::kHostDisplay;
+    uint8_t *d_bytes = to_host ? nullptr : (uint8_t *)out.p;  // the device's bytes: the display images, or the uint8 samples of 8-bit planes
+    int rc = ICER_RESULT_OK;
+    if (to_host && (display || bits == 8)) {                 // (a host call: they go through a buffer of the decoder's)
+        icerx_decoder::Buf &buf = display ? d->disp : d->out8;
+        HIP_TRY(ensure(buf, r.planes_total()));
+        d_bytes = (uint8_t *)buf.p;
+    }
+    if (display)
+        ICER_LAUNCH(display_finish_kernel, dim3((unsigned)(((r.frame_stride + 3u) / 4u + 255u) / 256u), (unsigned)n), 256, 0, r.d_planes,
+                    r.frame_stride, channels, r.d_frames, bits, d_bytes);
+    else
+        ICER_LAUNCH(finish_kernel, r.grid_all(), 256, 0, r.d_planes, r.frame_stride, channels, r.d_frames, bits == 8 ? d_bytes : nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k < n && to_host; k++) {
+        const size_t samples = (size_t)r.frames[k].w * r.frames[k].h;
+        if (!samples) continue;
+        switch (out.kind) {
+        case BatchOut::kHostDisplay:
+            HIP_TRY(hipMemcpy(((uint8_t *const *)out.p)[k], d_bytes + (size_t)k * channels * r.frame_stride, channels * samples, hipMemcpyDeviceToHost));
+            break;
+        default:
+            for (int c = 0; c < channels; c++) {
+                const size_t at = ((size_t)k * channels + c) * r.frame_stride;
+                if (bits == 8) HIP_TRY(hipMemcpy(((void *const *)out.p)[k * channels + c], d_bytes + at, samples, hipMemcpyDeviceToHost));
+                else HIP_TRY(hipMemcpy(((void *const *)out.p)[k * channels + c], r.d_planes + at, sizeof(uint16_t) * samples, hipMemcpyDeviceToHost));
+            }
+        }
+    }
+done:
+    return rc;
+}
+
+// n streams: stream k = bytes [offsets[k], offsets[k] + lens[k]) of `data` (host memory, or device memory when
+// data_on_device).  Results: rcs[k], ws[k] / hs[k] (in: the values kept when stream k holds no valid packet), and `out`.
+int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_device, const size_t *offsets, const size_t *lens,
+                 BatchOut out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
+{
+    g_error.clear();
+    if (!d || n < 0 || (n && (!offsets || !lens || !rcs || !ws || !hs)) || (!out.p && n)) return ICER_INVALID_INPUT;
+    if (n == 0) return ICER_RESULT_OK;
+    size_t total_len = 0, max_len = 0;
+    for (int k = 0; k < n; k++) {
+        if (lens[k] && !data) return ICER_INVALID_INPUT;
+        total_len = std::max(total_len, offsets[k] + lens[k]);
+        max_len = std::max(max_len, lens[k]);
+    }
+    if (total_len >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", total_len);
+    if (frame_stride > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", frame_stride);
+
+    BatchRun r = {d, n, frame_stride, plane_bits(d->bits), std::vector<FrameInfo>((size_t)n), std::vector<DecodePlan>((size_t)n), {}, nullptr, nullptr, nullptr};
+    std::vector<PacketCandidate> cands;
+    for (int k = 0; k < n; k++) {
+        memset(&r.frames[k], 0, sizeof(FrameInfo));
+        r.frames[k].stream_off = (uint32_t)offsets[k];
+        r.frames[k].stream_len = (uint32_t)lens[k];
+    }
+    int rc = batch_packets(r, data, data_on_device, total_len, max_len, cands);
+    if (rc == ICER_RESULT_OK) rc = batch_plans(r, cands, rcs, ws, hs);
+    if (rc == ICER_RESULT_OK && r.planes_total()) {
+        rc = batch_chains(r, out);
+        if (rc == ICER_RESULT_OK) rc = batch_samples(r);
+        if (rc == ICER_RESULT_OK) rc = batch_results(r, out);
+    }
 #ifndef ICER_HOST_MOCK
     // (an error exit may leave launches of the size classes behind on the side streams: nothing of this call runs on after it)
     if (rc != ICER_RESULT_OK && d->side_ok) { for (hipStream_t st : d->side) (void)hipStreamSynchronize(st); (void)hipDeviceSynchronize(); (void)hipGetLastError(); }
@@ -710,7 +705,7 @@ int decompress_planes(void *const planes[], int channels, size_t *image_w, size_
     d->recon = eighths;
     const size_t off = 0;
     int frame_rc = ICER_RESULT_OK;
-    rc = decode_batch(d, 1, data, false, &off, &data_length, planes, nullptr, bufsize, &frame_rc, image_w, image_h);
+    rc = decode_batch(d, 1, data, false, &off, &data_length, {BatchOut::kHostPlanes, planes}, bufsize, &frame_rc, image_w, image_h);
     icerx_decoder_destroy(d);
     return rc != ICER_RESULT_OK ? rc : frame_rc;
 }
@@ -810,14 +805,14 @@ int icerx_decode_host(icerx_decoder *dec, int n, const uint8_t *data, const size
                       void *const *planes_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
 {
     if (!planes_out && n) return ICER_INVALID_INPUT;
-    return decode_batch(dec, n, data, false, offsets, lens, planes_out, nullptr, frame_stride, rcs, ws, hs);
+    return decode_batch(dec, n, data, false, offsets, lens, {BatchOut::kHostPlanes, planes_out}, frame_stride, rcs, ws, hs);
 }
 
 int icerx_decode_device(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
                         void *d_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
 {
     if (!d_out && n) return ICER_INVALID_INPUT;
-    return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, nullptr, d_out, frame_stride, rcs, ws, hs);
+    return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, {BatchOut::kDevPlanes, d_out}, frame_stride, rcs, ws, hs);
 }
 
 int icerx_decode_host_display(icerx_decoder *dec, int n, const uint8_t *data, const size_t *offsets, const size_t *lens,
@@ -826,14 +821,14 @@ int icerx_decode_host_display(icerx_decoder *dec, int n, const uint8_t *data, co
     if (!images_out && n) return ICER_INVALID_INPUT;
     for (int k = 0; k < n; k++)
         if (!images_out[k]) return ICER_INVALID_INPUT;
-    return decode_batch(dec, n, data, false, offsets, lens, nullptr, nullptr, frame_stride, rcs, ws, hs, images_out, nullptr);
+    return decode_batch(dec, n, data, false, offsets, lens, {BatchOut::kHostDisplay, images_out}, frame_stride, rcs, ws, hs);
 }
 
 int icerx_decode_device_display(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
                                 uint8_t *d_out, size_t frame_stride, int *rcs, size_t *ws, size_t *hs)
 {
     if (!d_out && n) return ICER_INVALID_INPUT;
-    return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, nullptr, nullptr, frame_stride, rcs, ws, hs, nullptr, d_out);
+    return decode_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, {BatchOut::kDevDisplay, d_out}, frame_stride, rcs, ws, hs);
 }
 
 int icerx_planes_to_display_device(const void *d_planes, int n_frames, int channels, size_t w, size_t h, size_t plane_stride,
@@ -869,7 +864,7 @@ int icerx_decompress_display(uint8_t *image, size_t *image_w, size_t *image_h, s
     const size_t off = 0;
     int frame_rc = ICER_RESULT_OK;
     uint8_t *const images[1] = {image};
-    rc = decode_batch(d, 1, datastream, false, &off, &data_length, nullptr, nullptr, image_bufsize_pixels, &frame_rc, image_w, image_h, images, nullptr);
+    rc = decode_batch(d, 1, datastream, false, &off, &data_length, {BatchOut::kHostDisplay, images}, image_bufsize_pixels, &frame_rc, image_w, image_h);
     icerx_decoder_destroy(d);
     return rc != ICER_RESULT_OK ? rc : frame_rc;
 }

@@ -558,7 +558,7 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
     int rc = ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits, stages = d->stages;
-    const int nplanes = bits == 8 ? kPlanes8 : kPlanes, sign_bit = bits == 8 ? 7 : 15;
+    const int nplanes = plane_bits(bits).nplanes, sign_bit = plane_bits(bits).sign_bit;
     const int recon = d->recon;
     const DPlanGeom geom = async_geom(d);
     uint8_t *ws = (uint8_t *)workspace;
@@ -577,11 +577,10 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     const uint32_t cus = grid_cus(d->n_cus);
     const auto grid = grid_blocks;
 
-    // which kernel decodes a chain: decode_batch's rule, decided on the device (ICER_DEC_WAVE read per call, as there)
+    // which kernel decodes a chain: decode_batch's rule (decoder_route.hpp), decided on the device (ICER_DEC_WAVE read per call, as there)
     DRouteRule rule;
     {
-        const char *m = getenv("ICER_DEC_WAVE");
-        rule.mode = (!m || !m[0]) ? -1 : m[0] == '0' ? 0 : m[0] == '1' ? 1 : 2;
+        rule.mode = dec_wave_mode();
         rule.nplanes = (uint32_t)nplanes;
         rule.ring_elems_max = (uint32_t)((65536u - sizeof(DecoderTables) - 256u - kStateBytes) / sizeof(uint16_t));
         size_t limit = resolve_planes_lds(d);
@@ -597,18 +596,7 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
         rule.planes_lds_limit = (uint32_t)limit;
     }
 
-#ifndef ICER_HOST_MOCK
-    if (!d->side_ok) {
-        bool made = true;
-        for (hipStream_t &s : d->side) made = made && create_side_stream(&s) == hipSuccess;
-        if (!made) {
-            for (hipStream_t &s : d->side) { if (s) (void)hipStreamDestroy(s); s = nullptr; }
-            (void)hipGetLastError();
-            return fail("the decoder could not create its side streams");
-        }
-        d->side_ok = true;
-    }
-#endif
+    if ((rc = ensure_side_streams(d)) != ICER_RESULT_OK) return rc;
     if (!d->events_ok) {
         bool made = hipEventCreateWithFlags(&d->fork, hipEventDisableTiming) == hipSuccess;
         for (hipEvent_t &e : d->join) made = made && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;

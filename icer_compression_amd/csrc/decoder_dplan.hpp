@@ -13,6 +13,7 @@
 
 #include "decoder_core.hpp"
 #include "decoder_plan.hpp"
+#include "decoder_route.hpp"
 #include "plan.hpp"
 
 namespace icer {
@@ -213,19 +214,13 @@ ICER_HD bool dplan_chain(const DPlanGeom &g, const DWalk &s, const DPlanResult &
     return true;
 }
 
-// ---- chain routing: which list a chain goes to, and its place in the list
+// ---- chain routing: which list a chain goes to, and its place in the list (DRouteRule, takes_planes, dwant_planes: decoder_route.hpp)
 // kernels: 0 = wave per plane, 1 + k = lane per plane of ring class k, kRouteThread = thread per chain
 constexpr int kRouteClasses = 4, kRouteThread = 1 + kRouteClasses, kRouteKernels = kRouteThread + 1;
 constexpr int kRouteBuckets = 33;                  // by chain area, largest first: bucket = clz(w * h)
-struct DRouteRule {
-    int mode;                                      // ICER_DEC_WAVE: -1 unset (by load), 0, 1, 2
-    uint32_t planes_lds_limit;                     // dynamic LDS the planes kernel may take
-    uint32_t ring_elems_max;                       // the largest row ring of the lane-per-plane kernel (class 0)
-    uint32_t nplanes;
-};
 ICER_HD int droute(const DRouteRule &r, const ChainDesc &c, uint32_t stream_len, bool want_planes)
 {
-    if (want_planes && c.fast && stream_len >= 4u && pw_lds_bytes(c.w, (int)r.nplanes) <= r.planes_lds_limit) return 0;
+    if (takes_planes(r, c, stream_len, want_planes)) return 0;
     const size_t e = ring_elems_for(c.w, (int)r.nplanes);
     if (r.mode == 0 || e > r.ring_elems_max) return kRouteThread;
     int k = 0;
@@ -238,11 +233,6 @@ ICER_HD int droute_bucket(const ChainDesc &c)
     int b = 0;
     for (uint32_t m = 0x80000000u; m && !(a & m); m >>= 1) b++;
     return b;
-}
-// the planes kernel by load (decode_batch): unless pinned, only while the fast chains are at most 12 per compute unit
-ICER_HD bool dwant_planes(int mode, uint32_t lut_ok, uint32_t n_fast, uint32_t n_cus)
-{
-    return mode != 0 && mode != 1 && lut_ok != 0u && (mode != -1 || n_fast <= 12u * n_cus);
 }
 
 // ---- inverse-transform positions: where value v of a line's [lows | highs] lands (the plain interleave; the uint8

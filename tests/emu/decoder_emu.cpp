@@ -5,6 +5,7 @@
 #include "../../icer_compression_amd/csrc/decoder_planes.hpp"
 #include "../../icer_compression_amd/csrc/decoder_core.hpp"
 #include "../../icer_compression_amd/csrc/decoder_plan.hpp"
+#include "../../icer_compression_amd/csrc/decoder_route.hpp"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -116,6 +117,25 @@ extern "C" void emu_decoder_stats(unsigned long long *out) { for (int i = 0; i <
 // the wave-per-plane kernel's zero runs since the process started: [runs taken, decisions they stood for]
 // dynamic LDS that decode_chains_planes_kernel takes for a chain `w` samples wide (tests/decoder_batch_cases.py)
 extern "C" size_t emu_pw_lds_bytes(uint32_t w, int planes) { return pw_lds_bytes(w, planes); }
+
+// route_batch_chains (decoder_route.hpp), decode_batch's host routing, on n chains given by w / h / fast / frame (stream_len: per
+// frame).  order[i]: which input chain stands at place i afterwards; out: n_fast, planes_lds, class_end[4], class_elems[4],
+// rest_ring_elems
+extern "C" void emu_route_chains(uint32_t n, const uint16_t *w, const uint16_t *h, const uint32_t *fast, const uint32_t *frame,
+                                 const uint32_t *stream_len, int want_planes, size_t planes_lds_limit, int nplanes, uint32_t *order,
+                                 uint64_t *out)
+{
+    std::vector<ChainDesc> chains(n);
+    for (uint32_t i = 0; i < n; i++) {
+        memset(&chains[i], 0, sizeof(ChainDesc));
+        chains[i].w = w[i]; chains[i].h = h[i]; chains[i].fast = fast[i]; chains[i].frame = frame[i]; chains[i].first = i;
+    }
+    const BatchRoute r = route_batch_chains(chains, [&](uint32_t f) { return stream_len[f]; }, want_planes != 0, planes_lds_limit, nplanes);
+    for (uint32_t i = 0; i < n; i++) order[i] = chains[i].first;
+    *out++ = r.n_fast; *out++ = r.planes_lds;
+    for (int k = 0; k < kRingClasses; k++) { out[k] = r.class_end[k]; out[kRingClasses + k] = r.class_elems[k]; }
+    out[2 * kRingClasses] = r.rest_ring_elems;
+}
 
 extern "C" void emu_decoder_run_stats(unsigned long long *out) { out[0] = icer::g_pw_run_stats[0]; out[1] = icer::g_pw_run_stats[1]; }
 

@@ -24,7 +24,7 @@ u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 @pytest.fixture(scope="module")
 def emu():
     deps = [SRC] + [os.path.join(CSRC, f) for f in ("decoder_core.hpp", "decoder_plan.hpp", "decoder_wave.hpp", "decoder_planes.hpp", "wave.hpp", "plan.hpp",
-                                                    "icer_tables.hpp")]
+                                                    "icer_tables.hpp", "decoder_route.hpp")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-DICER_WAVE_EMU", "-o", LIB, SRC])
     lib = C.CDLL(LIB)
@@ -228,6 +228,98 @@ def test_wave_per_plane_kernel_schedules_and_shapes(emu, orc):
     finally:
         emu.lib.emu_decoder_order_seed(0)
         emu.lib.emu_decoder_mode(0)
+
+
+ROUTE_CLASSES = 4
+ROUTE_WIDTHS = (1, 2, 3, 17, 64, 65, 511, 512, 2048, 4096)
+
+
+def _ring_elems(w, nplanes):
+    """ring_elems_for (decoder_wave.hpp), restated: rows of the ring times its even pitch"""
+    rows = nplanes + 3 + (2 * (nplanes - 1) + max(w, 1) - 1) // max(w, 1)
+    return rows * (2 if w < 2 else (w + 1) & ~1)
+
+
+def _route_inputs(seed):
+    """200 seeded random chains (w, h, fast, frame) over 8 frames, and the degenerate lists; stream_len per frame"""
+    rng = np.random.default_rng(seed)
+    stream_len = [int(v) for v in rng.choice((0, 3, 4, 100), 8)]
+    rand = [(int(rng.choice(ROUTE_WIDTHS)), int(rng.integers(1, 4097)), int(rng.integers(0, 2)), int(rng.integers(0, 8))) for _ in range(200)]
+    lists = {"random": rand, "no_chains": [], "all_fast": [(w, h, 1, f) for w, h, _, f in rand], "none_fast": [(w, h, 0, f) for w, h, _, f in rand],
+             "one_width": [(64, h, fast, f) for _, h, fast, f in rand]}
+    return stream_len, lists
+
+
+def _route_parent(chains, stream_len, want_planes, limit, nplanes, pw_lds):
+    """decode_batch's routing as it stood before route_batch_chains, restated (stable partition; each share stably sorted by
+    (uint32_t)w * h descending; ring classes relative to the widest ring of the non-fast share; stable sort by class)"""
+    def takes(c):
+        return bool(want_planes and c[2] and stream_len[c[3]] >= 4 and pw_lds(c[0]) <= limit)
+
+    def cls(c):
+        k = 0
+        while k + 1 < ROUTE_CLASSES and _ring_elems(c[0], nplanes) * 2 <= (widest >> k):
+            k += 1
+        return k
+    idx = list(range(len(chains)))
+    fast = sorted([i for i in idx if takes(chains[i])], key=lambda i: -(chains[i][0] * chains[i][1]))
+    rest = sorted([i for i in idx if not takes(chains[i])], key=lambda i: -(chains[i][0] * chains[i][1]))
+    widest = max([2] + [_ring_elems(chains[i][0], nplanes) for i in rest])
+    rest = sorted(rest, key=lambda i: cls(chains[i]))
+    class_end, class_elems, at = [], [], 0
+    for k in range(ROUTE_CLASSES):
+        elems = 2
+        while at < len(rest) and cls(chains[rest[at]]) == k:
+            elems = max(elems, _ring_elems(chains[rest[at]][0], nplanes))
+            at += 1
+        class_end.append(len(fast) + at)
+        class_elems.append(elems)
+    return {"order": fast + rest, "n_fast": len(fast), "planes_lds": max([0] + [pw_lds(chains[i][0]) for i in fast]),
+            "class_end": class_end, "class_elems": class_elems, "rest_ring_elems": widest}
+
+
+@pytest.mark.parametrize("want_planes", [True, False], ids=["planes", "no_planes"])
+@pytest.mark.parametrize("limit", [0, 48 * 1024, 150 * 1024])
+@pytest.mark.parametrize("nplanes", [9, 7])
+def test_route_batch_chains(emu, nplanes, limit, want_planes):
+    """route_batch_chains (decoder_route.hpp) -- which kernel takes a chain of a synchronous batch decode, the launch order, the
+    four ring classes and the LDS of each launch: host arithmetic that decoded pixels never show (they do not depend on the
+    order, and on the LDS figures only by not faulting).  Equal, entry for entry, to the rule as decode_batch had it inline, and
+    the properties the launches rely on -- above all that a launch's LDS holds every ring it serves."""
+    lib = emu.lib
+    lib.emu_pw_lds_bytes.restype = C.c_size_t
+    lib.emu_pw_lds_bytes.argtypes = [C.c_uint32, C.c_int]
+    u16p, u32p = (np.ctypeslib.ndpointer(dtype=t, flags="C_CONTIGUOUS") for t in (np.uint16, np.uint32))
+    lib.emu_route_chains.restype = None
+    lib.emu_route_chains.argtypes = [C.c_uint32, u16p, u16p, u32p, u32p, u32p, C.c_int, C.c_size_t, C.c_int, u32p,
+                                     np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")]
+
+    def pw_lds(w):
+        return int(lib.emu_pw_lds_bytes(w, nplanes))
+    stream_len, lists = _route_inputs(20261020 + nplanes)
+    for name, chains in lists.items():
+        n = len(chains)
+        col = [np.array([c[j] for c in chains] + [0], dtype=t) for j, t in enumerate((np.uint16, np.uint16, np.uint32, np.uint32))]
+        order, out = np.full(n + 1, 0xFFFFFFFF, np.uint32), np.zeros(3 + 2 * ROUTE_CLASSES, np.uint64)
+        lib.emu_route_chains(n, *col, np.array(stream_len, np.uint32), int(want_planes), limit, nplanes, order, out)
+        order, out = [int(v) for v in order[:n]], [int(v) for v in out]
+        got = {"order": order, "n_fast": out[0], "planes_lds": out[1], "class_end": out[2:2 + ROUTE_CLASSES],
+               "class_elems": out[2 + ROUTE_CLASSES:2 + 2 * ROUTE_CLASSES], "rest_ring_elems": out[2 + 2 * ROUTE_CLASSES]}
+        assert got == _route_parent(chains, stream_len, want_planes, limit, nplanes, pw_lds), name          # 1. the parent's rule
+        assert sorted(order) == list(range(n)), name                                                         # 2. a permutation
+        n_fast, ends = got["n_fast"], got["class_end"]
+        takes = {i for i, c in enumerate(chains) if want_planes and c[2] and stream_len[c[3]] >= 4 and pw_lds(c[0]) <= limit}
+        assert set(order[:n_fast]) == takes and len(takes) == n_fast, name                                   # 3. the predicate
+        assert got["planes_lds"] == max([0] + [pw_lds(chains[i][0]) for i in order[:n_fast]]), name          # 4. the planes launch
+        assert ends == sorted(ends) and ends[0] >= n_fast and ends[-1] == n, (name, ends)                    # 6. the classes
+        area = [chains[i][0] * chains[i][1] for i in order]
+        for lo, hi in zip([0, n_fast] + ends[:-1], [n_fast] + ends):                                         # 5. longest first
+            assert all(area[i] >= area[i + 1] for i in range(lo, hi - 1)), (name, lo, hi)
+        for k, (lo, hi) in enumerate(zip([n_fast] + ends[:-1], ends)):                                       # 7. LDS of a launch
+            assert all(_ring_elems(chains[i][0], nplanes) <= got["class_elems"][k] for i in order[lo:hi]), (name, k)
+        assert all(_ring_elems(chains[i][0], nplanes) <= got["rest_ring_elems"] for i in order[n_fast:]), name
+        if name == "random" and want_planes and limit == 48 * 1024:
+            assert 0 < n_fast < n and len(set(ends)) > 2, (n_fast, ends)             # (the inputs reach both kernels and several classes)
 
 
 def test_host_pipeline_on_a_mock_hip_runtime(orc, tmp_path):
