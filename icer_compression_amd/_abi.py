@@ -82,6 +82,8 @@ _async = [p, i, p, sz, p, sz, p, p, sz, p, p, p, p, sz, p]       # icerx_decode_
 _masters = [p, i, p, sz, p, sz, p]                               # recutter, n, blob, its bytes, offsets, stride, lens
 _cut_out = [p, sz, p, p]                                         # out, its stride, sizes, rcs
 _work = [p, sz, p]                                               # workspace, its bytes, stream
+_sync_win = [p, i, p, szp, szp, p, p, sz, sz, ip, szp, szp, p]   # the synchronous window calls (icer_hip_dec_window.h)
+_async_win = [p, i, p, sz, p, sz, p, p, p, sz, sz, p, p, p, p] + _work
 
 DECODER = {
     "icer_get_image_dimensions": (i, [u8p, sz, szp, szp]),
@@ -125,6 +127,15 @@ DECODER = {
     # refinement increments: the difference and the union of two stored streams
     "icerx_combine_workspace_bytes": (sz, [p, i, sz]),
     "icerx_combine_device_async": (i, [p, i, i, p, sz, p, sz, p, p, sz, p, sz] + _cut_out + [p] + _work),
+    # window decode: a rectangle of each image, without the chains it does not depend on (include/icer_hip_dec_window.h)
+    "icerx_decode_host_window": (i, _sync_win),
+    "icerx_decode_device_window": (i, _sync_win),
+    "icerx_decode_device_window_display": (i, _sync_win),
+    "icerx_decode_window_workspace_bytes": (sz, [p, i, sz, sz]),
+    "icerx_decode_device_window_async": (i, _async_win),
+    "icerx_decode_window_display_workspace_bytes": (sz, [p, i, sz, sz]),
+    "icerx_decode_device_window_display_async": (i, _async_win),
+    "icerx_decompress_window": (i, [handle, i, szp, szp, sz, u8p, sz, i, i, u, i, i, i, p, p]),
     "icerx_decoder_last_error": (text, []),
     **_wavelets("icer_inverse_wavelet_transform"),
     "icer_from_sign_magnitude_int16": (None, [p, sz]),

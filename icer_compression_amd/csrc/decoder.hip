@@ -300,6 +300,7 @@ struct icerx_decoder {
     // device buffers, grown on demand and kept
     struct Buf { void *p = nullptr; size_t cap = 0; };
     Buf data, frames, crc, dtables, count, cands, chains, work, tmp, out8, pos, list, err, disp;
+    Buf win, wout;                     // a window decode (decoder_window.hpp): the frames' geometry, the windows of a host call
     int n_cus = 256;                   // compute units of the device
     bool planes_lds_raised = false;    // decode_chains_planes_kernel has been granted more than 64 KiB of dynamic LDS
     int is_gfx950 = -1;                // (-1: not asked yet)
@@ -418,6 +419,9 @@ struct BatchRun {
     const uint8_t *d_data;
     FrameInfo *d_frames;
     uint16_t *d_planes;
+    // a window decode (decoder_window.hpp): n x 4 x, y, w, h, and the samples a window may have; frame_stride is then the working planes'
+    const uint32_t *windows = nullptr;
+    size_t out_stride = 0;
     size_t planes_total() const { return (size_t)n * d->channels * frame_stride; }
     dim3 grid_all() const { return dim3((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * d->channels)); }
 };
@@ -476,7 +480,12 @@ int batch_plans(BatchRun &r, const std::vector<PacketCandidate> &cands, int *rcs
         while (at < cands.size() && cands[at].frame == (uint32_t)k) mine.push_back(cands[at++]);
         DecodePlan &pl = r.plans[k];
         FrameInfo &f = r.frames[k];
-        plan_decode(&pl, mine, d->channels, d->stages, d->segments, d->bits, ws[k], hs[k], r.frame_stride, d->reduce);
+        if (r.windows) {
+            const FilterTaps taps = filter_taps(d->filt);
+            plan_decode_window(&pl, mine, d->channels, d->stages, d->segments, d->bits, ws[k], hs[k], r.frame_stride, d->reduce,
+                               r.windows + 4 * (size_t)k, r.out_stride, taps.be == 0 && taps.am1 == 0);
+        } else
+            plan_decode(&pl, mine, d->channels, d->stages, d->segments, d->bits, ws[k], hs[k], r.frame_stride, d->reduce);
         ws[k] = pl.w; hs[k] = pl.h; rcs[k] = pl.rc;
         const bool runs = !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
         f.w = runs ? (uint32_t)pl.w : 0u;
@@ -712,6 +721,7 @@ int decompress_planes(void *const planes[], int channels, size_t *image_w, size_
 
 }  // namespace
 
+#include "decoder_window.hpp"          // the window decode: decode_window_batch, and what decode_async enqueues for a window call
 #ifdef ICER_DECODE_ASYNC
 #include "decoder_async.hpp"
 #include "recut.hpp"                   // icerx_recut_device_async: stored streams re-cut to smaller byte quotas
@@ -787,7 +797,7 @@ void icerx_decoder_destroy(icerx_decoder *d)
 {
     if (!d) return;
     for (icerx_decoder::Buf *b : {&d->data, &d->frames, &d->crc, &d->dtables, &d->count, &d->cands, &d->chains, &d->work, &d->tmp,
-                                  &d->out8, &d->pos, &d->list, &d->err, &d->disp})
+                                  &d->out8, &d->pos, &d->list, &d->err, &d->disp, &d->win, &d->wout})
         if (b->p) (void)hipFree(b->p);
 #ifndef ICER_HOST_MOCK
     if (d->side_ok) for (hipStream_t st : d->side) (void)hipStreamDestroy(st);
@@ -898,6 +908,93 @@ int icerx_decode_device_async(icerx_decoder *dec, int n, const void *d_data, siz
 {
     return decode_async(dec, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, d_out, frame_stride, d_rcs,
                         d_ws, d_hs, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+#endif
+
+// ---- window decode (include/icer_hip_dec_window.h)
+int icerx_decode_host_window(icerx_decoder *dec, int n, const uint8_t *data, const size_t *offsets, const size_t *lens,
+                             const uint32_t *windows, void *const *planes_out, size_t frame_stride, size_t full_stride, int *rcs,
+                             size_t *ws, size_t *hs, uint32_t *info)
+{
+    return decode_window_batch(dec, n, data, false, offsets, lens, windows, {BatchOut::kHostPlanes, planes_out}, frame_stride, full_stride,
+                               rcs, ws, hs, info);
+}
+
+int icerx_decode_device_window(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
+                               const uint32_t *windows, void *d_out, size_t frame_stride, size_t full_stride, int *rcs, size_t *ws,
+                               size_t *hs, uint32_t *info)
+{
+    return decode_window_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, windows, {BatchOut::kDevPlanes, d_out}, frame_stride,
+                               full_stride, rcs, ws, hs, info);
+}
+
+int icerx_decode_device_window_display(icerx_decoder *dec, int n, const void *d_data, const size_t *offsets, const size_t *lens,
+                                       const uint32_t *windows, uint8_t *d_out, size_t frame_stride, size_t full_stride, int *rcs,
+                                       size_t *ws, size_t *hs, uint32_t *info)
+{
+    return decode_window_batch(dec, n, (const uint8_t *)d_data, true, offsets, lens, windows, {BatchOut::kDevDisplay, d_out}, frame_stride,
+                               full_stride, rcs, ws, hs, info);
+}
+
+int icerx_decompress_window(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
+                            const uint8_t *datastream, size_t data_length, int stages, int filt, unsigned segments, int sample_bits,
+                            int reduce, int eighths, const uint32_t *window, uint32_t *info)
+{
+    if (!planes || (channels != 1 && channels != 3) || !image_w || !image_h || !window || !info || (!datastream && data_length) ||
+        eighths < 0 || eighths > kReconMax)
+        return ICER_INVALID_INPUT;
+    for (int c = 0; c < channels; c++)
+        if (!planes[c]) return ICER_INVALID_INPUT;
+    icerx_decoder *d = nullptr;
+    int rc = icerx_decoder_create_reduced(&d, -1, channels, stages, filt, segments, sample_bits, reduce);
+    if (rc != ICER_RESULT_OK) return rc;
+    d->recon = eighths;
+    // the working planes: the size of the image the stream's first valid packet announces, at the decoder's resolution
+    size_t fw = 0, fh = 0, full = 0;
+    if (datastream && icer_get_image_dimensions(datastream, data_length, &fw, &fh) == ICER_RESULT_OK) {
+        icerx_reduced_size(fw, fh, reduce, &fw, &fh);
+        full = fw * fh;
+    }
+    const size_t off = 0;
+    int frame_rc = ICER_RESULT_OK;
+    rc = decode_window_batch(d, 1, datastream, false, &off, &data_length, window, {BatchOut::kHostPlanes, planes}, bufsize, full, &frame_rc,
+                             image_w, image_h, info);
+    icerx_decoder_destroy(d);
+    return rc != ICER_RESULT_OK ? rc : frame_rc;
+}
+
+#ifdef ICER_DECODE_ASYNC
+size_t icerx_decode_window_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t full_stride)
+{
+    if (!dec || n <= 0) return 0;
+    return async_layout(dec, n, data_bytes, full_stride, true).total + window_geom_bytes(n);
+}
+
+size_t icerx_decode_window_display_workspace_bytes(const icerx_decoder *dec, int n, size_t data_bytes, size_t full_stride)
+{
+    return icerx_decode_window_workspace_bytes(dec, n, data_bytes, full_stride);
+}
+
+int icerx_decode_device_window_async(icerx_decoder *dec, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                     size_t stream_stride, const uint64_t *d_lens, const uint32_t *d_windows, void *d_out,
+                                     size_t frame_stride, size_t full_stride, int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs,
+                                     uint32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (n > 0 && (!d_out || !d_windows || !d_info)) return ICER_INVALID_INPUT;
+    const WindowCall win = {d_windows, d_info, full_stride};
+    return decode_async(dec, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, d_out, frame_stride, d_rcs, d_ws,
+                        d_hs, d_workspace, workspace_bytes, (hipStream_t)stream, nullptr, &win);
+}
+
+int icerx_decode_device_window_display_async(icerx_decoder *dec, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
+                                             size_t stream_stride, const uint64_t *d_lens, const uint32_t *d_windows, uint8_t *d_out,
+                                             size_t frame_stride, size_t full_stride, int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs,
+                                             uint32_t *d_info, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (n > 0 && (!d_out || !d_windows || !d_info)) return ICER_INVALID_INPUT;
+    const WindowCall win = {d_windows, d_info, full_stride};
+    return decode_async(dec, n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, nullptr, frame_stride, d_rcs, d_ws,
+                        d_hs, d_workspace, workspace_bytes, (hipStream_t)stream, d_out, &win);
 }
 #endif
 

@@ -545,17 +545,25 @@ fatal_frames_kernel(const uint32_t *__restrict__ ferr, int32_t *__restrict__ rcs
 // ------------------------------------------------------------------------------------------ host side
 int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets, size_t stream_stride,
                  const uint64_t *d_lens, void *d_out, size_t frame_stride, int32_t *d_rcs, uint64_t *d_ws, uint64_t *d_hs,
-                 void *workspace, size_t workspace_bytes, hipStream_t st, uint8_t *d_display = nullptr)
+                 void *workspace, size_t workspace_bytes, hipStream_t st, uint8_t *d_display = nullptr, const WindowCall *win = nullptr)
 {
     // (d_display: a display call -- d_out is null, the images go to d_display through display_finish_kernel)
+    // (win: a window decode, decoder_window.hpp -- the working planes, win->full_stride samples each, live in the workspace;
+    // d_out / d_display take the windows, of at most frame_stride samples)
     g_error.clear();
     if (!d || n < 0) return ICER_INVALID_INPUT;
     if (n == 0) return ICER_RESULT_OK;
     if (!d_lens || (!d_out && !d_display) || !d_rcs || !d_ws || !d_hs || !workspace || (data_bytes && !d_data)) return ICER_INVALID_INPUT;
+    if (win && (!win->d_windows || !win->d_info)) return ICER_INVALID_INPUT;
+    const size_t out_stride = frame_stride;
+    if (win) {
+        if (out_stride > 0xFFFFFFFFull) return fail("windows of %zu samples: 32-bit indices only", out_stride);
+        frame_stride = win->full_stride;                     // (from here on: the stride of the working planes)
+    }
     if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
     if (frame_stride > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", frame_stride);
-    const AsyncLayout L = async_layout(d, n, data_bytes, frame_stride, d_display != nullptr);
-    if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
+    const AsyncLayout L = async_layout(d, n, data_bytes, frame_stride, d_display != nullptr || win != nullptr);
+    if (workspace_bytes < L.total + (win ? window_geom_bytes(n) : 0u)) return ICER_INVALID_INPUT;
     int rc = ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits, stages = d->stages;
     const int nplanes = plane_bits(bits).nplanes, sign_bit = plane_bits(bits).sign_bit;
@@ -573,7 +581,8 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     const DecoderTables *tables = (const DecoderTables *)d->dtables.p;
     const uint32_t blob_len = (uint32_t)data_bytes, slots = (uint32_t)n * L.chain_slots;
     const size_t planes_total = (size_t)n * channels * frame_stride;
-    uint16_t *planes = bits == 16 && !d_display ? (uint16_t *)d_out : (uint16_t *)(ws + L.work);
+    uint16_t *planes = bits == 16 && !d_display && !win ? (uint16_t *)d_out : (uint16_t *)(ws + L.work);
+    WinGeom *win_geoms = (WinGeom *)(ws + L.total);           // (a window decode: behind everything else)
     const uint32_t cus = grid_cus(d->n_cus);
     const auto grid = grid_blocks;
 
@@ -619,6 +628,12 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
                    d_lens, recs, head, geom, (uint64_t)frame_stride, (uint32_t *)(ws + L.blob.tab_off), (uint32_t *)(ws + L.blob.tab_bits),
                    chains, frames, d_rcs, d_ws, d_hs);
     HIP_TRY(hipGetLastError());
+    if (win) {                                               // the chains the windows do not depend on leave their slots
+        const FilterTaps taps = filter_taps(d->filt);
+        ICER_LAUNCH_ON(st, window_frames_kernel, (unsigned)n, kPlanThreads, 0, win->d_windows, geom, (uint64_t)out_stride,
+                       taps.be == 0 && taps.am1 == 0, bits, chains, frames, d_rcs, win_geoms, win->d_info);
+        HIP_TRY(hipGetLastError());
+    }
     if (planes_total == 0) goto done;
 
     // 3. bit planes
@@ -657,7 +672,13 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
     }
 
     // 4. samples
-    {
+    if (win) {
+        rc = enqueue_window_samples(d, n, planes, (int16_t *)(ws + L.tmp), frame_stride, frames, win_geoms, pos, chains, slots, recon,
+                                    d_display ? (void *)d_display : d_out, out_stride, d_display != nullptr, frame_stride, st);
+        if (rc != ICER_RESULT_OK) goto done;
+        ICER_LAUNCH_ON(st, fatal_frames_kernel, ((unsigned)n + 255u) / 256u, 256, 0, ferr, d_rcs, (uint32_t)n);
+        HIP_TRY(hipGetLastError());
+    } else {
         const dim3 grid_all((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * channels));
         if (recon != 0 && slots) {                           // (behind the joins: every chain kernel is complete)
             ICER_LAUNCH_ON(st, reconstruct_kernel, dim3(slots, kReconParts), kReconThreads, 0, planes, frame_stride, channels,

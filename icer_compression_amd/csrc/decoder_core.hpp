@@ -737,8 +737,11 @@ ICER_HD int32_t dec_floordiv(int32_t a, int32_t b)            // icer_floor_div_
 // layout going to position pos_of[v] (the plain interleave, except for the uint8 routine's odd lines -- see
 // interleave_positions).  `bits` = 8: int8 storage (truncating stores), icer_wavelet.c:298-383.
 // `pos`: a position functor, pos(v) = pos_of[v] (PosTable) or computed (decoder_dplan.hpp DPos)
+// k_stop (<= n / 2; the window decode): the pairs below it are left alone -- restored high k needs restored high k + 1, so the
+// walk starts at the end of the line whatever is wanted
 template <class Pos>
-ICER_HD void idwt_line_at(const int16_t *src, int16_t *dst, uint32_t n, size_t stride, const FilterTaps f, int bits, Pos pos_of)
+ICER_HD void idwt_line_at(const int16_t *src, int16_t *dst, uint32_t n, size_t stride, const FilterTaps f, int bits, Pos pos_of,
+                          const uint32_t k_stop = 0)
 {
     const uint32_t nl = (n + 1u) / 2u, nh = n / 2u;
     const bool odd = (n & 1u) != 0;
@@ -747,7 +750,7 @@ ICER_HD void idwt_line_at(const int16_t *src, int16_t *dst, uint32_t n, size_t s
 #define RR(k) ((int32_t)(int16_t)(LO((k) - 1) - LO(k)))             /* get_r_int16 :206-208 (QUIRK W1b: wraps) */
 #define TR(v) (bits == 8 ? (int16_t)(int8_t)(v) : (int16_t)(v))
     int32_t next_hi = 0;                                             // restored high k + 1
-    for (uint32_t it = 0; it < nh; it++) {
+    for (uint32_t it = 0; it < nh - k_stop; it++) {
         const uint32_t k = nh - 1u - it;
         int32_t add;
         if (k == 0) add = dec_floordiv(RR(1), 4);

@@ -214,6 +214,19 @@ ICER_HD bool dplan_chain(const DPlanGeom &g, const DWalk &s, const DPlanResult &
     return true;
 }
 
+// ---- window decode: is chain slot j of a w x h frame kept by the frame's window?  (win_keeps with the slot's rectangle:
+// plan_decode_window's answer, decoder_plan.hpp)
+ICER_HD bool dplan_window_keeps(const DPlanGeom &g, const WinGeom &win, uint64_t w, uint64_t h, uint32_t j)
+{
+    const uint32_t sg = j % g.segments, sb = (j / g.segments) % 4u, lv = j / (g.segments * 4u) / g.channels + 1u;
+    uint64_t sw, sh, ox, oy;
+    dsubband(w, h, (int)lv, (int)sb, &sw, &sh, &ox, &oy);
+    SegmentGrid grid;
+    if (dmake_grid(&grid, sw, sh, g.segments) != kOk) return true;
+    const Rect r = dgrid_rect(grid, sg);
+    return win_keeps(win, (int)lv, (int)sb, r.x, r.y, r.w, r.h);
+}
+
 // ---- chain routing: which list a chain goes to, and its place in the list (DRouteRule, takes_planes, dwant_planes: decoder_route.hpp)
 // kernels: 0 = wave per plane, 1 + k = lane per plane of ring class k, kRouteThread = thread per chain
 constexpr int kRouteClasses = 4, kRouteThread = 1 + kRouteClasses, kRouteKernels = kRouteThread + 1;

@@ -9,6 +9,7 @@
 #pragma once
 #include <algorithm>
 #include <stdint.h>
+#include <utility>
 #include <vector>
 
 #include "decoder_core.hpp"
@@ -108,6 +109,86 @@ ICER_HD uint32_t payload_piece_crc(const uint32_t *tab, const uint8_t *s, const 
 // a side of the image at 1 / 2^r size: ceil(v / 2^r) (r < kMaxStages)
 ICER_HD uint64_t reduced_dim(uint64_t v, int r) { return (v + ((uint64_t(1) << r) - 1)) >> r; }
 
+// ------------------------------------------------------------------------------------------ window decode: the rule
+// A window decode (include/icer_hip_dec_window.h) delivers a rectangle of the image, and runs only the chains that rectangle
+// depends on.  The dependence is written down per line: of a line of n stored samples [nl lows | nh highs] whose restored
+// samples [a, b) are wanted, the stored lows [lo0, lo1) and highs [hi0, hi1) are needed.
+//   whole      n < 8, or a position table that is not the plain interleave (the odd lines of an 8-bit decoder): all of it
+//   filter A   (pairwise: beta = 0 and alpha_-1 = 0) restored high k reads stored high k and the lows k - 1 .. k + 1
+//   the rest   restored high k reads restored high k + 1, and alpha_-1 the low k - 2: everything from pair a / 2 - 2 on
+// win_geom chains the lines of the levels: the wanted rectangle of a level is the needed LL rectangle of the next finer one.
+struct WinAxis { uint32_t n, a, b, lo0, lo1, hi0, hi1, whole; };
+struct WinLevel { WinAxis x, y; };
+struct WinGeom {
+    uint32_t active;                 // the frame is transformed: its chains and passes are restricted to the window
+    uint32_t skip;                   // the window holds more samples than the output stride: nothing runs, nothing is written
+    uint32_t x0, y0, ww, wh;         // the window clipped to the image the frame runs with
+    uint32_t nlev, w;                // levels of the transform; the image width (the row pitch of the working planes)
+    WinLevel lv[kMaxStages];         // lv[0]: level 1, the finest
+};
+ICER_HD WinAxis win_axis(uint32_t n, uint32_t a, uint32_t b, bool pairwise, int bits)
+{
+    WinAxis r;
+    const uint32_t nl = (n + 1u) / 2u, nh = n / 2u;
+    r.n = n; r.a = a; r.b = b; r.whole = 0u;
+    r.lo0 = r.lo1 = r.hi0 = r.hi1 = 0u;
+    if (a >= b) { r.a = r.b = 0u; return r; }
+    if (n < 8u || (bits == 8 && (n & 1u))) { r.whole = 1u; r.lo1 = nl; r.hi1 = nh; return r; }
+    const uint32_t ka = a >> 1, kb = (b - 1u) >> 1;
+    if (pairwise) {
+        r.hi1 = kb + 1u < nh ? kb + 1u : nh;
+        r.hi0 = ka < r.hi1 ? ka : r.hi1;
+        r.lo0 = ka ? ka - 1u : 0u;
+        r.lo1 = kb + 2u < nl ? kb + 2u : nl;
+    } else {
+        r.hi1 = nh;
+        r.hi0 = ka < nh ? ka : nh;
+        r.lo0 = ka >= 2u ? ka - 2u : 0u;
+        r.lo1 = nl;
+    }
+    return r;
+}
+// the pairs of a line that its inverse pass restores for the wanted samples: [k0, k1), k = nh standing for the last low of an odd line
+ICER_HD void win_pairs(const WinAxis &ax, uint32_t *k0, uint32_t *k1)
+{
+    if (ax.a >= ax.b) { *k0 = *k1 = 0u; return; }
+    if (ax.whole) { *k0 = 0u; *k1 = (ax.n + 1u) / 2u; return; }
+    *k0 = ax.a >> 1; *k1 = ((ax.b - 1u) >> 1) + 1u;
+}
+// `runs`: the frame delivers samples (w x h of them); `transformed`: it reaches the inverse transform and that has levels.
+// win = x, y, w, h in pixels of the w x h image; out_stride: samples the caller has room for.
+ICER_HD void win_geom(WinGeom *g, uint64_t w, uint64_t h, int stages, bool runs, bool transformed, const uint32_t *win,
+                      uint64_t out_stride, bool pairwise, int bits)
+{
+    const uint64_t iw = runs ? w : 0u, ih = runs ? h : 0u;
+    const uint64_t x0 = win[0] < iw ? win[0] : iw, y0 = win[1] < ih ? win[1] : ih;
+    const uint64_t ww = win[2] < iw - x0 ? win[2] : iw - x0, wh = win[3] < ih - y0 ? win[3] : ih - y0;
+    const bool empty = ww == 0u || wh == 0u;
+    g->x0 = (uint32_t)x0; g->y0 = (uint32_t)y0; g->ww = empty ? 0u : (uint32_t)ww; g->wh = empty ? 0u : (uint32_t)wh;
+    g->skip = (!empty && ww * wh > out_stride) ? 1u : 0u;
+    g->active = (runs && transformed) ? 1u : 0u;
+    g->nlev = (uint32_t)stages; g->w = (uint32_t)iw;
+    uint32_t xa = g->x0, xb = g->x0 + g->ww, ya = g->y0, yb = g->y0 + g->wh;
+    if (g->skip) xa = xb = ya = yb = 0u;
+    for (int j = 0; j < kMaxStages; j++) {
+        const bool on = g->active && j < stages;
+        const uint32_t cw = on ? (uint32_t)((w + ((uint64_t(1) << j) - 1)) >> j) : 0u, ch = on ? (uint32_t)((h + ((uint64_t(1) << j) - 1)) >> j) : 0u;
+        g->lv[j].x = win_axis(cw, on ? xa : 0u, on ? xb : 0u, pairwise, bits);
+        g->lv[j].y = win_axis(ch, on ? ya : 0u, on ? yb : 0u, pairwise, bits);
+        xa = g->lv[j].x.lo0; xb = g->lv[j].x.lo1; ya = g->lv[j].y.lo0; yb = g->lv[j].y.lo1;
+    }
+}
+// is the chain of the segment rectangle (rx, ry, rw, rh) of subband `sb` at level `lv` (1 = finest) kept?
+ICER_HD bool win_keeps(const WinGeom &g, int lv, int sb, uint64_t rx, uint64_t ry, uint64_t rw, uint64_t rh)
+{
+    if (g.skip) return false;
+    if (!g.active) return true;
+    const WinAxis &ax = g.lv[lv - 1].x, &ay = g.lv[lv - 1].y;
+    const uint64_t x0 = (sb & 1) ? ax.hi0 : ax.lo0, x1 = (sb & 1) ? ax.hi1 : ax.lo1;
+    const uint64_t y0 = (sb & 2) ? ay.hi0 : ay.lo0, y1 = (sb & 2) ? ay.hi1 : ay.lo1;
+    return rx < x1 && rx + rw > x0 && ry < y1 && ry + rh > y0;
+}
+
 struct DecodeLevel { uint32_t cw, ch; };        // region of one inverse-transform level (deepest first)
 
 struct DecodePlan {
@@ -117,14 +198,19 @@ struct DecodePlan {
     uint16_t mean[3] = {0, 0, 0};
     std::vector<ChainDesc> chains;
     std::vector<DecodeLevel> levels;            // empty when the deepest LL is thinner than 3 (ICER_TOO_MANY_STAGES, ignored)
+    // a window decode (`window` given): the frame's geometry, and the chains the plain call runs (`chains` holds the kept ones)
+    WinGeom win = {};
+    uint32_t chains_full = 0;
 };
 
 // `cands`: the candidates of ONE stream, sorted by offset.  *w / *h: in = the caller's values (kept when the stream holds no valid packet).
 // `reduce` = r > 0 (a reduced-resolution decoder, include/icer_hip_dec.h): `stages` is the decoder's S - r, and the walk reads
 // the stream as its derived stream -- a valid packet of level <= r moves the cursor and nothing else, any other counts as
 // level - r of an image of ceil(w / 2^r) x ceil(h / 2^r).
+// `where` (window decode): of each chain its level and its rectangle inside its subband.
 inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cands, int channels,
-                        int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce = 0)
+                        int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce = 0,
+                        std::vector<std::pair<int, Rect>> *where = nullptr)
 {
     const int planes = sample_bits == 8 ? kPlanes8 : kPlanes;
     *pl = DecodePlan();
@@ -186,6 +272,7 @@ inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cand
                     for (int lsb = planes - 1; lsb >= 0 && c.pkt[lsb] != kNoPacket; lsb--)
                         if (bits_tab[slot_index(ch, lv, sb, (int)sg, lsb)] < kFastPacketBits) c.fast = 0u;
                     pl->chains.push_back(c);
+                    if (where) where->push_back({lv, rects[sg]});
                 }
             }
     if (pl->rc != kOk) return;
@@ -193,6 +280,26 @@ inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cand
     if (dim_low(w, stages) >= 3 && dim_low(h, stages) >= 3)
         for (int it = 1; it <= stages; it++)
             pl->levels.push_back(DecodeLevel{(uint32_t)dim_low(w, stages - it), (uint32_t)dim_low(h, stages - it)});
+}
+
+// The plan of a window decode (`window`: x, y, w, h in pixels of the delivered image): the plan of the plain call, less the
+// chains the window does not depend on (win_keeps) -- pl->win, pl->chains_full.  A window of more than out_stride samples turns
+// rc into ICER_BYTE_QUOTA_EXCEEDED and keeps no chain.  `pairwise`: the decoder's filter has no recurrence along a line (filter A).
+inline void plan_decode_window(DecodePlan *pl, const std::vector<PacketCandidate> &cands, int channels, int stages, unsigned segments,
+                               int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce, const uint32_t *window,
+                               size_t out_stride, bool pairwise)
+{
+    std::vector<std::pair<int, Rect>> where;
+    plan_decode(pl, cands, channels, stages, segments, sample_bits, w_in, h_in, bufsize, reduce, &where);
+    const bool runs = !(pl->rc == kInvalidInput || pl->rc == kTooManyStages || pl->rc == kByteQuotaExceeded) && pl->w * pl->h > 0;
+    win_geom(&pl->win, pl->w, pl->h, stages, runs, pl->transform && !pl->levels.empty(), window, out_stride, pairwise, sample_bits);
+    pl->chains_full = runs ? (uint32_t)pl->chains.size() : 0u;
+    std::vector<ChainDesc> kept;
+    for (size_t i = 0; i < pl->chains.size(); i++)
+        if (win_keeps(pl->win, where[i].first, (int)pl->chains[i].subband, where[i].second.x, where[i].second.y, where[i].second.w, where[i].second.h))
+            kept.push_back(pl->chains[i]);
+    pl->chains.swap(kept);
+    if (pl->win.skip) pl->rc = kByteQuotaExceeded;
 }
 
 }  // namespace icer

@@ -24,6 +24,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libicer_hip_dec.so")
 ICER_DECODER_OUT_OF_DATA = -7
 ICER_DECODED_INVALID_DATA = -8
+WINDOW_INFO = 6                  # uint32 per frame of a window decode: x0, y0, ww, wh, chains run, chains of the plain call
 
 _lib = None
 _sz = C.c_size_t
@@ -124,14 +125,32 @@ def reduced_size(w: int, h: int, r: int):
 
 
 def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: int, bufsize: int | None = None, bits: int = 16,
-               lib=None, reduce: int = 0, reconstruct: int = 0):
+               lib=None, reduce: int = 0, reconstruct: int = 0, window=None):
     """icer_decompress_image_[yuv_]uint16 / _uint8 on a host stream -> (rc, w, h, [flat planes of bufsize samples]).
+    window = (x, y, w, h) in pixels of the delivered image: icerx_decompress_window, only that rectangle, stored compactly, and
+    only the chains it depends on -> (rc, w, h, [flat planes], info) with info = [x0, y0, ww, wh, chains run, chains of the
+    plain call]; bufsize then counts samples of the window (default: the window clipped to the image the stream announces).
     reduce = r > 0: icerx_decompress_reduced, the image at 1/2^r size; bufsize then counts samples of the reduced image.
     reconstruct = k in 1..4: icerx_decompress_reconstructed, truncated non-zero coefficients rebuilt k eighths of the way into
     their interval (3 is the recommended value; 0 is the reference's decode)."""
     lib = lib or load_library()
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
+    if window is not None:
+        fn = _need(lib, "icerx_decompress_window")
+        if bufsize is None:                                  # (the window clipped to the image the stream announces)
+            rc0, w0, h0 = icer_get_image_dimensions(stream, lib)
+            w0, h0 = reduced_size(w0, h0, reduce) if rc0 == 0 else (0, 0)
+            x0, y0 = min(int(window[0]), w0), min(int(window[1]), h0)
+            bufsize = min(int(window[2]), w0 - x0) * min(int(window[3]), h0 - y0)
+        buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
+        planes = [np.zeros(max(bufsize, 1), np.uint16 if bits == 16 else np.uint8) for _ in range(channels)]
+        ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
+        win, info = np.asarray(window, np.uint32).copy(), np.zeros(WINDOW_INFO, np.uint32)
+        w, h = _sz(0), _sz(0)
+        rc = fn(ptrs, channels, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, bits, reduce, reconstruct,
+                win.ctypes.data, info.ctypes.data)
+        return rc, w.value, h.value, planes, [int(x) for x in info]
     if bufsize is None:
         rc, w, h = icer_get_image_dimensions(stream, lib)
         if reduce > 0:
@@ -224,6 +243,7 @@ class Decoder:
         self.channels, self.bits, self.reduce = channels, bits, 0
         self._workspaces = {}                # decode_torch: one cached workspace per torch stream
         self._display_workspaces = {}        # decode_display_torch: the same, sized for the display call
+        self._window_workspaces = {}         # decode_window_torch: the same, sized for the window calls
         self.handle = C.c_void_p()
         if reduce != 0:
             fn = _need(self.lib, "icerx_decoder_create_reduced")
@@ -345,6 +365,81 @@ class Decoder:
         need = self.display_workspace_bytes(n, data.numel(), frame_stride) if n else 0
         _enqueue(self.lib, "icerx_decode_device_display_async", self._display_workspaces, need, data.device, self.decode_display_async_ptrs,
                  n, data, data.numel(), offsets, stream_stride, lens, out, frame_stride, rcs, ws, hs)
+
+    # ---- window decode: a rectangle of each image, without the chains it does not depend on (include/icer_hip_dec_window.h) ----
+    def _sync_window(self, fn, n: int, data: int, offsets, lens, windows, out, frame_stride: int, full_stride: int):
+        """one of the three synchronous window calls; windows: n x 4 (x, y, w, h) -> (rc, rcs, ws, hs, info as n lists of 6)"""
+        m = max(n, 1)
+        offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
+        rcs, ws, hs = (C.c_int * m)(), (_sz * m)(), (_sz * m)()
+        win = np.zeros((m, 4), np.uint32)
+        win[:n] = np.asarray(windows, np.uint32).reshape(n, 4)
+        info = np.zeros((m, WINDOW_INFO), np.uint32)
+        rc = fn(self.handle, n, data, offs, ln, win.ctypes.data, out, frame_stride, full_stride, rcs, ws, hs, info.ctypes.data)
+        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n], [[int(x) for x in row] for row in info[:n]]
+
+    def decode_window_host(self, streams, windows, frame_stride: int, full_stride: int):
+        """icerx_decode_host_window -> (rc, [(rc_k, w_k, h_k, [flat planes of frame_stride samples], info_k)]): the first
+        ww * wh samples of each plane are the window, row by row"""
+        fn = _need(self.lib, "icerx_decode_host_window")
+        n, ch = len(streams), self.channels
+        planes = [np.zeros(max(frame_stride, 1), np.uint16 if self.bits == 16 else np.uint8) for _ in range(n * ch)]
+        blob, offs, lens = self._pack(streams)
+        ptrs = (C.c_void_p * max(n * ch, 1))(*[a.ctypes.data for a in planes])
+        rc, rcs, ws, hs, info = self._sync_window(fn, n, blob.ctypes.data, offs, lens, windows, ptrs, frame_stride, full_stride)
+        return rc, [(rcs[k], ws[k], hs[k], planes[k * ch: (k + 1) * ch], info[k]) for k in range(n)]
+
+    def decode_window_device(self, n: int, d_data: int, offsets, lens, windows, d_out: int, frame_stride: int, full_stride: int,
+                             display: bool = False):
+        """icerx_decode_device_window / _display on raw device pointers (windows: a host sequence) -> (rc, rcs, ws, hs, info)"""
+        fn = _need(self.lib, "icerx_decode_device_window_display" if display else "icerx_decode_device_window")
+        return self._sync_window(fn, n, d_data, offsets, lens, windows, d_out, frame_stride, full_stride)
+
+    def window_workspace_bytes(self, n: int, data_bytes: int, full_stride: int, display: bool = False) -> int:
+        """icerx_decode_window_workspace_bytes / _display_workspace_bytes: what one decode_window_async_ptrs call needs"""
+        name = "icerx_decode_window_display_workspace_bytes" if display else "icerx_decode_window_workspace_bytes"
+        return int(_need(self.lib, name)(self.handle, n, data_bytes, full_stride))
+
+    def decode_window_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, d_windows: int,
+                                 d_out: int, frame_stride: int, full_stride: int, d_rcs: int, d_ws: int, d_hs: int, d_info: int,
+                                 d_workspace: int, workspace_bytes: int, stream: int = 0, display: bool = False) -> int:
+        """icerx_decode_device_window_async / _display_async on raw device pointers (as decode_device_async_ptrs; d_windows:
+        n x 4 uint32 and d_info: n x 6 uint32 in device memory)"""
+        fn = _need(self.lib, "icerx_decode_device_window_display_async" if display else "icerx_decode_device_window_async")
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_windows, d_out, frame_stride, full_stride, d_rcs,
+                  d_ws, d_hs, d_info, d_workspace, workspace_bytes, stream)
+
+    def decode_window_torch(self, data, lens, out, rcs, ws, hs, windows, info, full_stride: int, offsets=None, stream_stride=None,
+                            display: bool = False) -> None:
+        """decode_torch (display=True: decode_display_torch) for a rectangle per frame, on torch's current stream, without waiting.
+
+        windows: a cuda int32 / uint32 tensor (n, 4) of x, y, w, h in pixels of the delivered image, read on the stream (write
+        it there with any torch op just before; nothing waits); info: cuda int32 (n, 6), written with x0, y0, ww, wh of the
+        clipped window, the chains run and the chains the plain call runs.  out holds n * channels * frame_stride samples (bytes
+        for display): the window of frame k, ww * wh samples row by row, at the start of each of its planes (of its row).
+        full_stride: samples of a full-size working plane (in the workspace), at least the largest image.  Only the chains a
+        window depends on are run."""
+        import torch
+        n = int(lens.shape[0])
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        want = (torch.uint8,) if display or self.bits == 8 else (torch.int16, getattr(torch, "uint16", torch.int16))
+        i32 = (torch.int32, getattr(torch, "uint32", torch.int32))
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("rcs", rcs, torch.int32), ("ws", ws, torch.int64),
+                      ("hs", hs, torch.int64), ("out", out, want), ("offsets", offsets, torch.int64), ("windows", windows, i32),
+                      ("info", info, i32))
+        if tuple(windows.shape) != (n, 4) or info.numel() != n * WINDOW_INFO:
+            raise ValueError("windows must be (n, 4) and info n * 6 entries")
+        if n and out.numel() % (n * self.channels):
+            raise ValueError("out must hold n * channels * frame_stride samples")
+        frame_stride = out.numel() // (n * self.channels) if n else 0
+        need = self.window_workspace_bytes(n, data.numel(), full_stride, display) if n else 0
+        name = "icerx_decode_device_window_display_async" if display else "icerx_decode_device_window_async"
+
+        def call(n_, data_, bytes_, offs_, sstride_, lens_, win_, out_, fs_, full_, rcs_, ws_, hs_, info_, work_, work_bytes_, stream_):
+            return self.decode_window_async_ptrs(n_, data_, bytes_, offs_, sstride_, lens_, win_, out_, fs_, full_, rcs_, ws_, hs_, info_,
+                                                 work_, work_bytes_, stream_, display)
+        _enqueue(self.lib, name, self._window_workspaces, need, data.device, call, n, data, data.numel(), offsets, stream_stride, lens,
+                 windows, out, frame_stride, int(full_stride), rcs, ws, hs, info)
 
     def decode_torch(self, data, lens, out, rcs, ws, hs, offsets=None, stream_stride=None) -> None:
         """Decode n streams of a cuda uint8 tensor on torch's current stream, without waiting (icerx_decode_device_async).

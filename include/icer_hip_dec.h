@@ -441,6 +441,12 @@ void icer_from_sign_magnitude_int8(uint8_t *data, size_t len);
 int icerx_wavelet_inverse_device(void *d_planes, int n_planes, size_t w, size_t h, size_t plane_stride, int stages, int filt,
                                  int sample_bits, void *d_workspace, int32_t *d_rcs, void *stream);
 
+/* The window decode -- a rectangle of each image, skipping the chains it does not depend on: icerx_decode_*_window*,
+ * icerx_decompress_window.  Declared and described in icer_hip_dec_window.h. */
+#define ICER_HIP_DEC_H_WINDOW_PART 1
+#include "icer_hip_dec_window.h"
+#undef ICER_HIP_DEC_H_WINDOW_PART
+
 #ifdef __cplusplus
 }
 #endif
