@@ -52,6 +52,9 @@ ENCODER = {
     "icerx_encode_device_roi": (i, [p, p, i, p, i, szp, i, p, sz, p, p, p, p, p]),
     "icerx_target_threshold": (u64, [p, dbl]),
     "icerx_get_distortion_table": (i, [p, i, p, sz]),
+    # the distortion sidecar: a frame's energy table and LL means in device memory (include/icer_hip_sidecar.h)
+    "icerx_distortion_sidecar_entries": (sz, [p]),
+    "icerx_get_distortion_sidecar_device": (i, [p, i, p, sz, p]),
     "icerx_encode_host": (i, [p, p, i, sz, p, sz, p, p]),
     "icerx_device_count": (i, []),
     "icerx_compress_batch_uint16": (i, _batch + [i]),
@@ -124,6 +127,14 @@ DECODER = {
     "icerx_recut_device_cuts_async": (i, _masters + [ip, szp, i] + _cut_out + _work),
     "icerx_recut_roi_workspace_bytes": (sz, [p, i, sz, i]),
     "icerx_recut_device_roi_async": (i, _masters + [p, ip, ip, szp, i] + _cut_out + [p, p] + _work),
+    # re-cutting to a distortion target or a shared byte budget, by the masters' distortion sidecars (include/icer_hip_dec_quality.h)
+    "icerx_recutter_create_quality": (i, [handle, i, sz, sz, i, i, i, u, i, i]),
+    "icerx_recut_sidecar_entries": (sz, [p]),
+    "icerx_recut_target_threshold": (u64, [p, dbl, i]),
+    "icerx_recut_target_workspace_bytes": (sz, [p, i, sz, i]),
+    "icerx_recut_device_target_async": (i, _masters + [p, sz, ip, C.POINTER(dbl), i, sz] + _cut_out + [p, p, p] + _work),
+    "icerx_recut_budget_workspace_bytes": (sz, [p, i, sz, i]),
+    "icerx_recut_device_budget_async": (i, _masters + [p, sz, i, C.POINTER(u64), i, sz] + _cut_out + [p, p, p, p, p] + _work),
     # refinement increments: the difference and the union of two stored streams
     "icerx_combine_workspace_bytes": (sz, [p, i, sz]),
     "icerx_combine_device_async": (i, [p, i, i, p, sz, p, sz, p, p, sz, p, sz] + _cut_out + [p] + _work),

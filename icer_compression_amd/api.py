@@ -323,6 +323,30 @@ class Encoder:
         _check("icerx_get_distortion_table", rc, ": no target call yet, or the frame was not part of the last one")
         return dst
 
+    @property
+    def sidecar_entries(self) -> int:
+        """icerx_distortion_sidecar_entries: the uint64 words of a frame's distortion sidecar, families * (P + 1) + 1"""
+        return int(self.lib.icerx_distortion_sidecar_entries(self.handle))
+
+    def distortion_sidecar_torch(self, n_frames: int | None = None, out=None):
+        """the distortion sidecars of the first n_frames frames (default: max_frames) of the last target or budget call
+        (icerx_get_distortion_sidecar_device): a cuda int64 tensor (n_frames, sidecar_entries) holding the uint64 words -- a
+        frame's energy table as distortion_table gives it, then one word with its LL means --, written on torch's current
+        stream without a host copy.  out: a cuda int64 tensor (n_frames, stride) with stride >= sidecar_entries and unit
+        stride along a row, to write into; the words behind a row's entries are left alone.  Store a row beside the frame's
+        master: decoder.Recutter re-cuts the master to a distortion target or a shared byte budget by it."""
+        import torch
+        n = self.max_frames if n_frames is None else int(n_frames)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((n, self.sidecar_entries), dtype=torch.int64, device=dev)
+        if not out.is_cuda or out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] < n or out.stride(1) != 1:
+            raise ValueError("out must be a cuda int64 tensor (n_frames, stride) with rows of consecutive words")
+        rc = self.lib.icerx_get_distortion_sidecar_device(self.handle, n, out.data_ptr(), out.stride(0) if out.shape[0] > 1 else out.shape[1],
+                                                          torch.cuda.current_stream(dev).cuda_stream)
+        _check("icerx_get_distortion_sidecar_device", rc, ": no target or budget call yet, more frames than it had, or rows too short")
+        return out
+
     def encode_torch_s8(self, planes, byte_quota: int):
         """uint8 twins: planes = cuda uint8 tensor (n, h, w) or (n, channels, h, w), int8 storage; the encoder must have
         been created with sample_bits=8.  Returns [(rc, stream bytes)] per frame."""

@@ -1354,6 +1354,24 @@ int icerx_get_distortion_table(icerx_encoder *e, int frame, uint64_t *dst, size_
     return 0;
 }
 
+// The distortion sidecar (include/icer_hip_sidecar.h): the table above with the frame's LL means behind it, into device memory.
+size_t icerx_distortion_sidecar_entries(const icerx_encoder *e)
+{
+    return e ? (size_t)e->plan.n_families * ((size_t)(e->sample_bits == 8 ? kPlanes8 : kPlanes) + 1) + 1 : 0;
+}
+
+int icerx_get_distortion_sidecar_device(icerx_encoder *e, int n_frames, uint64_t *d_dst, size_t stride_entries, void *stream)
+{
+    if (!e || !d_dst || !e->dist.p || !e->means.p || n_frames < 1 || n_frames > e->dist_frames) return ICER_INVALID_INPUT;
+    const size_t entries = icerx_distortion_sidecar_entries(e);
+    if (stride_entries < entries) return ICER_INVALID_INPUT;
+    HIP_TRY(hipSetDevice(e->device));
+    hipLaunchKernelGGL(sidecar_export_kernel, dim3((unsigned)((entries + 255) / 256), (unsigned)n_frames), dim3(256), 0, (hipStream_t)stream, e->dist.p,
+                       e->means.p, e->channels, (uint32_t)(entries - 1), reinterpret_cast<unsigned long long *>(d_dst), stride_entries);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // The 8-bit front ends: converted into the encoder's own planes on `stream`, then icerx_encode_device on those.
 static int encode_converted(const char *entry, int bits, int channels, const char *needs, Convert how, icerx_encoder *e, const uint8_t *d_src, int n_frames,
                             size_t byte_quota, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, void *stream)

@@ -725,7 +725,8 @@ int decompress_planes(void *const planes[], int channels, size_t *image_w, size_
 #ifdef ICER_DECODE_ASYNC
 #include "decoder_async.hpp"
 #include "recut.hpp"                   // icerx_recut_device_async: stored streams re-cut to smaller byte quotas
-#include "combine.hpp"                 // icerx_combine_device_async: the union and the difference of two stored streams of a frame
+#include "recut_quality.hpp"           // icerx_recut_device_target_async / _budget_async: stored streams re-cut by their distortion sidecars
+#include "combine.hpp"               // icerx_combine_device_async: the union and the difference of two stored streams of a frame
 #endif
 
 extern "C" {

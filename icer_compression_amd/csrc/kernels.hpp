@@ -913,6 +913,22 @@ scan_target_kernel(const uint32_t *__restrict__ unit_bits, const uint32_t *__res
     if (flags && threadIdx.x == 0) atomicOr(bound_overflow, (int)flags);
 }
 
+// The distortion sidecar of every frame (icerx_get_distortion_sidecar_device): row f of `dst`, `stride` words apart, takes the
+// `per_frame` entries of the frame's E and one word with its LL means, channel c in bits 16 c .. 16 c + 15.
+// grid = (ceil((per_frame + 1) / 256), frames), block = 256.
+__global__ void __launch_bounds__(256)
+sidecar_export_kernel(const unsigned long long *__restrict__ E, const uint16_t *__restrict__ means, int channels, uint32_t per_frame,
+                      unsigned long long *__restrict__ dst, size_t stride)
+{
+    const uint32_t frame = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > per_frame) return;
+    unsigned long long v = 0;
+    if (i < per_frame) v = E[(size_t)frame * per_frame + i];
+    else
+        for (int c = 0; c < channels; c++) v |= (unsigned long long)means[(size_t)frame * channels + c] << (16 * c);
+    dst[(size_t)frame * stride + i] = v;
+}
+
 // ------------------------------------------------------------------------------------------ byte budget
 // The streams of one coded batch cut so that they share a byte budget at equal distortion (icerx_encode_device_budget),
 // budget-major as the target call is target-major.

@@ -46,11 +46,30 @@ struct icerx_recutter {
         void *prio = nullptr;                         // the priority of every unit's packet (roi_priorities): the ROI call's
     } red[kRecutMaxReduce + 1];
     uint32_t units_total = 0;                         // red[0 .. max_reduce].n_units together
+    // a quality recutter (icerx_recutter_create_quality, recut_quality.hpp): the filter the masters were made with, and per
+    // geometry what prepare_target of the encoder library gives an encoder of it -- every family's weight, channel and LL term --
+    // and for r > 0 fam_map[g]: the family of the master that family g of that geometry is.  fam_cap: per family of the
+    // master, the most its E[.][P] can be (coefficients x max_mag^2).  filt < 0: a plain recutter, none of this.
+    int filt = -1;
+    struct Quality {
+        uint32_t n_families = 0;
+        void *weight = nullptr, *chan = nullptr, *ll_term = nullptr, *fam_map = nullptr;
+    } qual[kRecutMaxReduce + 1];
+    void *fam_cap = nullptr;
+    uint32_t families_total = 0;                      // qual[0 .. max_reduce].n_families together
 };
 
 extern "C" void icerx_recutter_destroy(icerx_recutter *r);
 
 namespace {
+
+// the tables of a quality recutter on the host: built and checked before anything is allocated (recut_quality.hpp)
+struct RecutQualityHost {
+    std::vector<uint32_t> weight[kRecutMaxReduce + 1], chan[kRecutMaxReduce + 1], fam_map[kRecutMaxReduce + 1];
+    std::vector<unsigned long long> ll_term[kRecutMaxReduce + 1], fam_cap;
+};
+int recut_quality_build(const std::vector<Plan> &plans, const DPlanGeom &geom, int filt, int sample_bits, RecutQualityHost *q);
+int recut_quality_upload(icerx_recutter *r, const RecutQualityHost &q);
 
 #ifdef ICER_HOST_MOCK
 constexpr uint32_t kRecutPlanThreads = 1, kRecutGatherThreads = 3;    // (the mock runs a workgroup's threads one after the other)
@@ -479,8 +498,10 @@ done:
     return rc;
 }
 
+// quality: a quality recutter for masters made with filter `filt` (recut_quality.hpp); its tables are built and checked on the
+// host before anything is allocated
 int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, unsigned segments, int sample_bits,
-                    int max_reduce)
+                    int max_reduce, bool quality = false, int filt = -1)
 {
     g_error.clear();
     if (!out) return ICER_INVALID_INPUT;
@@ -496,6 +517,10 @@ int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int ch
         const int krc = build_plan(&plans[k], (size_t)reduced_dim(w, k), (size_t)reduced_dim(h, k), channels, stages - k, segs, sample_bits);
         if (krc != kOk) return krc;
     }
+    const DPlanGeom geom{(uint32_t)channels, (uint32_t)stages, segments, (uint32_t)(sample_bits == 8 ? kPlanes8 : kPlanes)};
+    RecutQualityHost qual;
+    if (quality)
+        if (const int qrc = recut_quality_build(plans, geom, filt, sample_bits, &qual)) return qrc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail("no usable HIP device");
 #ifndef ICER_HOST_MOCK
@@ -506,7 +531,7 @@ int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int ch
 #endif
     icerx_recutter *r = new icerx_recutter;
     r->device = device; r->w = w; r->h = h; r->max_reduce = max_reduce;
-    r->geom = DPlanGeom{(uint32_t)channels, (uint32_t)stages, segments, (uint32_t)(sample_bits == 8 ? kPlanes8 : kPlanes)};
+    r->geom = geom;
 #ifndef ICER_HOST_MOCK
     { int cur = 0; hipDeviceProp_t prop; if (hipGetDevice(&cur) == hipSuccess && hipGetDeviceProperties(&prop, cur) == hipSuccess && prop.multiProcessorCount > 0) r->n_cus = prop.multiProcessorCount; }
 #endif
@@ -532,6 +557,10 @@ int recutter_create(icerx_recutter **out, int device, size_t w, size_t h, int ch
         for (size_t u = 0; u < slot0.size(); u++) full_to_cut[u] = of_slot[slot0[u]];
         HIP_TRY(recut_upload(&g.full_to_cut, full_to_cut.data(), sizeof(uint32_t) * full_to_cut.size()));
     }
+    if (quality) {
+        r->filt = filt;
+        if ((rc = recut_quality_upload(r, qual)) != ICER_RESULT_OK) goto done;
+    }
     *out = r;
     return ICER_RESULT_OK;
 done:
@@ -550,6 +579,10 @@ void icerx_recutter_destroy(icerx_recutter *r)
     for (int k = 0; k <= kRecutMaxReduce; k++)
         for (void *p : {r->red[k].unit_slot, r->red[k].final_order, r->red[k].units, r->red[k].full_to_cut, r->red[k].prio})
             if (p) (void)hipFree(p);
+    for (int k = 0; k <= kRecutMaxReduce; k++)
+        for (void *p : {r->qual[k].weight, r->qual[k].chan, r->qual[k].ll_term, r->qual[k].fam_map})
+            if (p) (void)hipFree(p);
+    if (r->fam_cap) (void)hipFree(r->fam_cap);
     delete r;
 }
 

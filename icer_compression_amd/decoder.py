@@ -484,17 +484,24 @@ class Recutter:
     any decoder made for stages - r decodes (the re-cut of the master's derived stream, include/icer_hip_dec.h)."""
 
     def __init__(self, w: int, h: int, channels: int, stages: int, segments: int, bits: int = 16, device: int = -1, lib=None,
-                 max_reduce: int = 0):
+                 max_reduce: int = 0, filt=None):
         self.lib = lib or load_library()
         _need(self.lib, "icerx_recut_device_async")
         self.w, self.h, self.channels, self.bits = w, h, channels, bits
         L = self.lib
+        self._target_workspaces, self._budget_workspaces = {}, {}        # recut_target_torch / recut_budget_torch: a cache each, as below
         self._workspaces = {}                # recut_torch: one cached workspace per torch stream
         self._cuts_workspaces = {}           # recut_cuts_torch: the same, sized for the cuts call
         self._roi_workspaces = {}            # recut_roi_torch: the same, sized for the ROI call
         self._combine_workspaces = {}        # combine_torch: the same, sized for the combine call
         self.handle = C.c_void_p()
         self.max_reduce = 0
+        self.filt = filt
+        if filt is not None:                 # a quality recutter: it knows the filter, and cuts by distortion sidecars as well
+            fn = _need(L, "icerx_recutter_create_quality")
+            _check(L, "icerx_recutter_create_quality", fn(C.byref(self.handle), device, w, h, channels, stages, filt, segments, bits, max_reduce))
+            self.max_reduce = int(L.icerx_recutter_max_reduce(self.handle))
+            return
         if max_reduce != 0:
             fn = _need(L, "icerx_recutter_create_reduced")
             _check(L, "icerx_recutter_create_reduced", fn(C.byref(self.handle), device, w, h, channels, stages, segments, bits, max_reduce))
@@ -510,6 +517,8 @@ class Recutter:
         self._cuts_workspaces.clear()
         self._roi_workspaces.clear()
         self._combine_workspaces.clear()
+        self._target_workspaces.clear()
+        self._budget_workspaces.clear()
 
     def __del__(self):
         try:
@@ -638,6 +647,132 @@ class Recutter:
         _enqueue(self.lib, "icerx_recut_device_roi_async", self._roi_workspaces, self.roi_workspace_bytes(n, data.numel(), Q), data.device,
                  self.recut_roi_device_async_ptrs, n, data, data.numel(), offsets, stream_stride, lens, rois, [c[0] for c in cuts],
                  [c[2] for c in cuts], [c[1] for c in cuts], out, out.shape[-1], sizes, rcs, kept, foreground)
+
+    # ---- cuts by distortion target or shared byte budget, from masters and their distortion sidecars (include/icer_hip_dec_quality.h) ----
+    @property
+    def sidecar_entries(self) -> int:
+        """icerx_recut_sidecar_entries: the uint64 words of a sidecar row (Encoder.sidecar_entries of the geometry); 0 for a plain recutter"""
+        return int(_need(self.lib, "icerx_recut_sidecar_entries")(self.handle))
+
+    def target_threshold(self, mse: float, reduce: int = 0) -> int:
+        """icerx_recut_target_threshold: floor(mse * samples at 1/2^reduce size * 16), saturated; at reduce 0 Encoder.target_threshold"""
+        return int(_need(self.lib, "icerx_recut_target_threshold")(self.handle, float(mse), int(reduce)))
+
+    def target_workspace_bytes(self, n: int, data_bytes: int, n_cuts: int) -> int:
+        """icerx_recut_target_workspace_bytes: the device workspace one recut_target_device_async_ptrs call needs"""
+        return int(_need(self.lib, "icerx_recut_target_workspace_bytes")(self.handle, n, data_bytes, n_cuts))
+
+    def recut_target_device_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, d_sidecar: int,
+                                       sidecar_stride: int, reduces, targets_mse, byte_cap: int, d_out: int, out_stride: int, d_sizes: int,
+                                       d_rcs: int, d_reached: int, d_dist: int, d_equiv_quota: int, d_workspace: int, workspace_bytes: int,
+                                       stream: int = 0, n_cuts=None) -> int:
+        """icerx_recut_device_target_async on raw device pointers (masters and outputs as recut_cuts_device_async_ptrs; d_sidecar:
+        uint64 rows sidecar_stride words apart; reduces: a host sequence or None for every reduce 0; targets_mse: a host
+        sequence, None for a null pointer; d_reached: int32, d_dist / d_equiv_quota: uint64, entry c * n + f as d_sizes).
+        Enqueues on `stream` and returns the call's rc without waiting."""
+        fn = _need(self.lib, "icerx_recut_device_target_async")
+        nc = n_cuts if n_cuts is not None else (len(targets_mse) if targets_mse is not None else 0)
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_sidecar, sidecar_stride, c_array(C.c_int, reduces),
+                  c_array(C.c_double, targets_mse), nc, byte_cap, d_out, out_stride, d_sizes, d_rcs, d_reached, d_dist, d_equiv_quota,
+                  d_workspace, workspace_bytes, stream)
+
+    def _quality_tensors(self, n, Q, data, lens, sidecar, out, offsets, int64s, int32s):
+        import torch
+        _need_tensors(("data", data, torch.uint8), ("lens", lens, torch.int64), ("sidecar", sidecar, torch.int64), ("out", out, torch.uint8),
+                      ("offsets", offsets, torch.int64), *[(k, t, torch.int64) for k, t in int64s.items()],
+                      *[(k, t, torch.int32) for k, t in int32s.items()])
+        if sidecar.dim() != 2 or sidecar.shape[0] < n:
+            raise ValueError("sidecar must be (n, stride) int64 words")
+        if out.dim() < 2 or out.numel() != Q * n * out.shape[-1] or any(t.numel() != Q * n for t in (*int64s.values(), *int32s.values())):
+            raise ValueError("out must be (Q * n, out_stride), " + ", ".join((*int64s, *int32s)) + " Q * n entries")
+
+    def recut_target_torch(self, data, lens, sidecar, cuts, byte_cap: int, out, sizes, rcs, reached, dist, equiv, offsets=None,
+                           stream_stride=None) -> None:
+        """recut_cuts_torch with cuts = [(reduce, mse), ...] and the masters' distortion sidecars: row and entry c * n + f hold frame
+        f cut where the mean squared error mse is met at 1/2^reduce size, or at byte_cap -- at reduce 0 what
+        Encoder.encode_target_torch gives on the original frames.  sidecar: cuda int64 (n, stride >= sidecar_entries), row f
+        the sidecar of master f (Encoder.distortion_sidecar_torch); reached: cuda int32, dist / equiv: cuda int64 of Q * n
+        entries.  Needs a quality recutter (filt given).  Everything else as recut_cuts_torch; the workspace is cached per
+        stream, apart from the other calls'."""
+        n, Q = int(lens.shape[0]), len(cuts)
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        self._quality_tensors(n, Q, data, lens, sidecar, out, offsets, dict(sizes=sizes, dist=dist, equiv=equiv), dict(rcs=rcs, reached=reached))
+        _enqueue(self.lib, "icerx_recut_device_target_async", self._target_workspaces, self.target_workspace_bytes(n, data.numel(), Q),
+                 data.device, self.recut_target_device_async_ptrs, n, data, data.numel(), offsets, stream_stride, lens, sidecar, sidecar.shape[1],
+                 [c[0] for c in cuts], [c[1] for c in cuts], int(byte_cap), out, out.shape[-1], sizes, rcs, reached, dist, equiv)
+
+    def budget_workspace_bytes(self, n: int, data_bytes: int, n_budgets: int) -> int:
+        """icerx_recut_budget_workspace_bytes: the device workspace one recut_budget_device_async_ptrs call needs"""
+        return int(_need(self.lib, "icerx_recut_budget_workspace_bytes")(self.handle, n, data_bytes, n_budgets))
+
+    def recut_budget_device_async_ptrs(self, n: int, d_data: int, data_bytes: int, d_offsets, stream_stride: int, d_lens: int, d_sidecar: int,
+                                       sidecar_stride: int, reduce: int, budgets, byte_cap: int, d_out: int, out_stride: int, d_sizes: int,
+                                       d_rcs: int, d_at_cap: int, d_dist: int, d_equiv_quota: int, d_threshold: int, d_total: int,
+                                       d_workspace: int, workspace_bytes: int, stream: int = 0, n_budgets=None) -> int:
+        """icerx_recut_device_budget_async on raw device pointers (as recut_target_device_async_ptrs; one reduce for the call;
+        budgets: a host sequence, None for a null pointer; d_threshold / d_total: uint64, entry b).  Enqueues on `stream` and
+        returns the call's rc without waiting."""
+        fn = _need(self.lib, "icerx_recut_device_budget_async")
+        nb = n_budgets if n_budgets is not None else (len(budgets) if budgets is not None else 0)
+        return fn(self.handle, n, d_data, data_bytes, d_offsets, stream_stride, d_lens, d_sidecar, sidecar_stride, reduce,
+                  c_array(C.c_uint64, budgets), nb, byte_cap, d_out, out_stride, d_sizes, d_rcs, d_at_cap, d_dist, d_equiv_quota, d_threshold,
+                  d_total, d_workspace, workspace_bytes, stream)
+
+    def recut_budget_torch(self, data, lens, sidecar, budgets, byte_cap: int, out, sizes, rcs, at_cap, dist, equiv, threshold, total, reduce: int = 0,
+                           offsets=None, stream_stride=None) -> None:
+        """recut_target_torch with byte budgets in place of the targets: row and entry b * n + f hold frame f when the n masters
+        share budgets[b] bytes at one distortion threshold, no stream above byte_cap, all at 1/2^reduce size -- at reduce 0 what
+        Encoder.encode_budget_torch gives on the original frames.  at_cap: cuda int32 of B * n entries; threshold / total: cuda
+        int64 (B,).  The workspace is cached per stream, apart from the other calls'."""
+        import torch
+        n, Q = int(lens.shape[0]), len(budgets)
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
+        self._quality_tensors(n, Q, data, lens, sidecar, out, offsets, dict(sizes=sizes, dist=dist, equiv=equiv), dict(rcs=rcs, at_cap=at_cap))
+        _need_tensors(("threshold", threshold, torch.int64), ("total", total, torch.int64))
+        if threshold.numel() != Q or total.numel() != Q:
+            raise ValueError("threshold and total must have an entry per budget")
+        _enqueue(self.lib, "icerx_recut_device_budget_async", self._budget_workspaces, self.budget_workspace_bytes(n, data.numel(), Q),
+                 data.device, self.recut_budget_device_async_ptrs, n, data, data.numel(), offsets, stream_stride, lens, sidecar, sidecar.shape[1],
+                 int(reduce), [int(b) for b in budgets], int(byte_cap), out, out.shape[-1], sizes, rcs, at_cap, dist, equiv, threshold, total)
+
+    def _quality_through(self, streams, sidecars, Q, byte_cap, call):
+        """bytes and sidecar rows in; call(blob, lens, offs, sidecar, out, sizes, rcs, flag, dist, equiv); -> per row a dict"""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        n = len(streams)
+        side = torch.from_numpy(np.ascontiguousarray(np.asarray(sidecars, np.uint64).reshape(n, -1)).view(np.int64)).to(dev)
+        flag = torch.zeros(Q * n, dtype=torch.int32, device=dev)
+        dist, equiv = (torch.zeros(Q * n, dtype=torch.int64, device=dev) for _ in range(2))
+        rows = _bytes_through(streams, Q * n, max(int(byte_cap), 1), lambda blob, lens, offs, out, sizes, rcs:
+                              call(blob, lens, offs, side, out, sizes, rcs, flag, dist, equiv))
+        flag, dist, equiv = flag.cpu().numpy(), dist.cpu().numpy().view(np.uint64), equiv.cpu().numpy().view(np.uint64)
+        return [dict(rc=rc, stream=s, flag=int(flag[k]), dist=int(dist[k]), equiv=int(equiv[k])) for k, (rc, s) in enumerate(rows)]
+
+    def recut_target(self, streams, sidecars, cuts, byte_cap: int):
+        """bytes in, bytes out: res[c][f] = dict(rc, stream, reached, dist, equiv) of master streams[f] with sidecar row sidecars[f]
+        (uint64 words) at cuts[c] = (reduce, mse) under byte_cap (copies to the device and back, and waits: a convenience, not the
+        fast path)"""
+        n, Q = len(streams), len(cuts)
+        rows = self._quality_through(streams, sidecars, Q, byte_cap, lambda blob, lens, offs, side, out, sizes, rcs, flag, dist, equiv:
+                                     self.recut_target_torch(blob, lens, side, cuts, byte_cap, out, sizes, rcs, flag, dist, equiv, offsets=offs))
+        for row in rows:
+            row["reached"] = row.pop("flag")
+        return [rows[c * n: (c + 1) * n] for c in range(Q)]
+
+    def recut_budget(self, streams, sidecars, budgets, byte_cap: int, reduce: int = 0):
+        """bytes in, bytes out: (res, thresholds, totals) with res[b][f] = dict(rc, stream, at_cap, dist, equiv) of master streams[f]
+        when the masters share budgets[b] bytes (copies to the device and back, and waits: a convenience, not the fast path)"""
+        import torch
+        n, Q = len(streams), len(budgets)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        threshold, total = (torch.zeros(Q, dtype=torch.int64, device=dev) for _ in range(2))
+        rows = self._quality_through(streams, sidecars, Q, byte_cap, lambda blob, lens, offs, side, out, sizes, rcs, flag, dist, equiv:
+                                     self.recut_budget_torch(blob, lens, side, budgets, byte_cap, out, sizes, rcs, flag, dist, equiv, threshold,
+                                                             total, reduce=reduce, offsets=offs))
+        for row in rows:
+            row["at_cap"] = row.pop("flag")
+        return ([rows[b * n: (b + 1) * n] for b in range(Q)], [int(t) for t in threshold.cpu().numpy().view(np.uint64)],
+                [int(t) for t in total.cpu().numpy().view(np.uint64)])
 
     # ---- refinement increments: the difference and the union of two stored streams (icerx_combine_device_async) ----
     def combine_workspace_bytes(self, n: int, data_bytes: int) -> int:

@@ -420,6 +420,13 @@ int icerx_wavelet_forward_device(void *d_planes, int n_planes, size_t w, size_t 
 
 const char *icerx_last_error(void);
 
+/* The distortion sidecar -- a frame's energy table and LL means in device memory, stored beside its master so that
+ * libicer_hip_dec.so can re-cut the master to a distortion target or a shared byte budget: icerx_distortion_sidecar_entries,
+ * icerx_get_distortion_sidecar_device.  Declared and described in icer_hip_sidecar.h. */
+#define ICER_HIP_H_SIDECAR_PART 1
+#include "icer_hip_sidecar.h"
+#undef ICER_HIP_H_SIDECAR_PART
+
 #ifdef __cplusplus
 }
 #endif

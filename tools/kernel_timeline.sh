@@ -2,6 +2,7 @@
 # Timeline of the kernels of ONE call (run on the GPU box):  tools/kernel_timeline.sh <out.txt> W H STAGES SEGMENTS FRAMES
 #   rocprofv3 --kernel-trace around tools/quick_bench.py; start / end of every dispatch of the last call relative to its first kernel, with the gaps
 #   TL_SCRIPT=tools/<script>.py: that script with the arguments after <out.txt> instead (a ladder, target or budget call: its last gather_* kernel ends the call)
+#   TL_FIRST / TL_LAST=<kernel name prefixes, comma separated>: the kernels that start and end the call instead (a re-cut call: mark_headers_kernel, recut_gather_kernel)
 set -u
 dst=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
@@ -25,10 +26,13 @@ st, en = ("start", "end") if "start" in cols else ("start_timestamp", "end_times
 rows = list(cur.execute(f"select {nm}, {st}, {en} from {view} order by {st}"))
 rows = [(n.replace("(anonymous namespace)::", "").split("(")[0].replace("icer::", "").replace("void ", "")[:48], s, e) for n, s, e in rows]
 # the last call: from the last clear_ranges_kernel / first dwt before the final gather_kernel
-last_gather = max(i for i, r in enumerate(rows) if r[0].startswith("gather_kernel") or r[0].startswith("gather_ladder_kernel"))
-# (a target or budget call clears its energy table with a fill in mid-call: only the clear kernel starts such a call)
 import os
+ends = tuple(os.environ["TL_LAST"].split(",")) if os.environ.get("TL_LAST") else ("gather_kernel", "gather_ladder_kernel")
+last_gather = max(i for i, r in enumerate(rows) if r[0].startswith(ends))
+# (a target or budget call clears its energy table with a fill in mid-call: only the clear kernel starts such a call)
 starts = ("clear_ranges_kernel",) if os.environ.get("TL_SCRIPT") else ("clear_ranges_kernel", "__amd_rocclr_fill")
+if os.environ.get("TL_FIRST"):
+    starts = tuple(os.environ["TL_FIRST"].split(","))
 i0 = max(i for i, r in enumerate(rows[:last_gather]) if r[0].startswith(starts))
 while i0 > 0 and rows[i0 - 1][0].startswith(starts) and rows[i0][1] - rows[i0 - 1][2] < 50000:
     i0 -= 1
