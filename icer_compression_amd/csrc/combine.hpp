@@ -2,11 +2,12 @@
 // frame, on the device.  A decoder files packets by (channel, level, subband, bit plane, segment) and does not mind their
 // order, so a held stream followed by the packets it lacks decodes as the larger stream does; this call computes those packets
 // (DIFFERENCE) and the canonical stream of both (UNION).  Included by decoder.hip after recut.hpp, whose recutter, blob stage,
-// frame walk and packet copy it uses; the rule itself is combine_core.hpp.
+// call record (RecutCall), masters (RecutMasters, one per operand), frame walk (recut_walk) and packet copy it uses; the rule
+// itself is combine_core.hpp.
 //
 //   blob       enqueue_blob_stage, once over the blob that holds both operands; two packet tables per frame (A's of frame k
 //              is table k, B's table n + k)
-//   frames     combine_plan_kernel, one workgroup per frame: walk_frame for A, then for B; the frame's status; a workgroup scan
+//   frames     combine_plan_kernel, one workgroup per frame: recut_walk for A, then for B; the frame's status; a workgroup scan
 //              of the kept packets' lengths along the final order -> per unit its offset in the result (~0: not kept), where
 //              its packet lies in the blob and its length; size, return code, counts
 //   packets    combine_gather_kernel, one workgroup per (unit, frame): header and payload in one copy (copy_unit_recut)
@@ -44,39 +45,31 @@ CombineLayout combine_layout(const icerx_recutter *r, int n, size_t data_bytes)
     return L;
 }
 
-// where the frames of an operand lie: frame k = blob bytes [off, off + lens[k]), off = offsets[k] or base + k * stream_stride
-struct CombineOperand {
-    const uint64_t *offsets, *lens;
-    uint64_t base;
+// what the plan leaves of every frame: row k of foff / from / bytes (n_units entries a row) in the workspace; entries 2 k and
+// 2 k + 1 of the caller's counts
+struct CombinePlan {
+    uint64_t *foff;
+    uint32_t *from, *bytes, *counts;
 };
 
-// one workgroup per frame, of any size.  Row k of foff / from / bytes (n_units entries a row), entry k of sizes / rcs, entries
-// 2 k and 2 k + 1 of counts.  A frame with a status, or whose result is longer than out_stride, keeps nothing (every foff ~0).
+// one workgroup per frame, of any size: the operands `a` and `b` as RecutMasters of one blob (A's tables are the first n, B's
+// the n behind them), the plan of the full geometry.  Entry k of o.sizes / o.rcs.  A frame with a status, or whose result is
+// longer than o.out_stride, keeps nothing (every foff ~0).
 __global__ void __launch_bounds__(256)
-combine_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, int op, CombineOperand a, CombineOperand b, uint64_t stream_stride,
-                    const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head, DPlanGeom geom, uint64_t image_w, uint64_t image_h,
-                    const uint32_t *__restrict__ unit_slot, const uint32_t *__restrict__ final_order, uint32_t n_units, uint64_t out_stride,
-                    uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits, uint64_t *__restrict__ foff, uint32_t *__restrict__ from,
-                    uint32_t *__restrict__ bytes, unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs,
-                    uint32_t *__restrict__ counts)
+combine_plan_kernel(RecutMasters a, RecutMasters b, int op, const uint32_t *__restrict__ unit_slot, const uint32_t *__restrict__ final_order,
+                    uint32_t n_units, CombinePlan p, RecutOut o)
 {
     ICER_DYNAMIC_LDS(uint8_t, lds);                            // combine_plan_lds(blockDim.x)
-    const uint32_t k = blockIdx.x, n = gridDim.x, tid = threadIdx.x, nth = blockDim.x;
-    const size_t slots = geom.slots();
-    const uint64_t off_a = a.offsets ? a.offsets[k] : a.base + (uint64_t)k * stream_stride;
-    const uint64_t off_b = b.offsets ? b.offsets[k] : b.base + (uint64_t)k * stream_stride;
-    uint32_t *to_a = tab_off + (size_t)k * slots, *tb_a = tab_bits + (size_t)k * slots;
-    uint32_t *to_b = tab_off + ((size_t)n + k) * slots, *tb_b = tab_bits + ((size_t)n + k) * slots;
-    WalkNotes notes;
-    DWalk s = walk_frame(lds, blob, blob_len, off_a, a.lens[k], recs, head, geom, image_w, image_h, to_a, tb_a, &notes);
-    const int status_a = recut_frame_status(notes.inside != 0u, s.cursor, notes.other_size != 0u);
+    const uint32_t k = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
+    const RecutTabRows ta = a.rows(k), tb = b.rows(k);
+    const uint64_t off_a = a.offset(k), off_b = b.offset(k);
+    const int status_a = recut_walk(lds, a, off_a, a.lens[k], ta).status;
     ICER_BARRIER();                                            // (every thread has read the first walk's result out of the LDS)
-    s = walk_frame(lds, blob, blob_len, off_b, b.lens[k], recs, head, geom, image_w, image_h, to_b, tb_b, &notes);
-    const int status_b = recut_frame_status(notes.inside != 0u, s.cursor, notes.other_size != 0u);
+    const int status_b = recut_walk(lds, b, off_b, b.lens[k], tb).status;
     const int status = combine_frame_status(op, status_a, status_b);
 
     // thread t takes positions [t * per, (t + 1) * per) of the final order: its sum, then its start from the sums before it
-    const CombineTables t{to_a, tb_a, to_b, tb_b};
+    const CombineTables t{ta.off, ta.bits, tb.off, tb.bits};
     CombineSum *parts = reinterpret_cast<CombineSum *>(lds + kCombinePartsAt);
     const uint32_t per = (n_units + nth - 1u) / nth;
     const uint32_t i0 = tid * per < n_units ? tid * per : n_units, i1 = n_units - i0 < per ? n_units : i0 + per;
@@ -92,15 +85,15 @@ combine_plan_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, int op,
         if (j == tid) at = all.bytes;
         all.bytes += parts[j].bytes; all.packets += parts[j].packets; all.from_a += parts[j].from_a;
     }
-    const bool place = status == kOk && all.bytes <= out_stride;
+    const bool place = status == kOk && all.bytes <= o.out_stride;
     // (an operand with a status of its own has no packet in its table, and its offset is not looked at)
-    combine_place_range(op, t, unit_slot, final_order, i0, i1, place, at, (uint32_t)off_a, (uint32_t)off_b, foff + (size_t)k * n_units,
-                        from + (size_t)k * n_units, bytes + (size_t)k * n_units);
+    combine_place_range(op, t, unit_slot, final_order, i0, i1, place, at, (uint32_t)off_a, (uint32_t)off_b, p.foff + (size_t)k * n_units,
+                        p.from + (size_t)k * n_units, p.bytes + (size_t)k * n_units);
     if (tid == 0) {
-        sizes[k] = status == kOk ? all.bytes : 0ull;
-        rcs[k] = status != kOk ? status : place ? kOk : kOutputBufTooSmall;
-        counts[2u * (size_t)k] = all.packets;
-        counts[2u * (size_t)k + 1u] = all.from_a;
+        o.sizes[k] = status == kOk ? all.bytes : 0ull;
+        o.rcs[k] = status != kOk ? status : place ? kOk : kOutputBufTooSmall;
+        p.counts[2u * (size_t)k] = all.packets;
+        p.counts[2u * (size_t)k + 1u] = all.from_a;
     }
 }
 
@@ -116,39 +109,45 @@ combine_gather_kernel(const uint8_t *__restrict__ blob, uint32_t n_units, const 
     copy_unit_recut(blob + from[at], bytes[at], foff + at, 0, 1u, out + (size_t)frame * out_stride, 0, threadIdx.x, blockDim.x);
 }
 
+// where the frames of an operand lie: frame k = blob bytes [off, off + lens[k]), off = offsets[k] or base + k * stream_stride
+struct CombineOperand {
+    const uint64_t *offsets, *lens;
+    uint64_t base;
+};
+
+// The call is a RecutCall without cuts and with no masters of its own (d_offsets, d_lens): the operands stand beside it.
 // Every check comes before the first thing enqueued: a refused call writes nothing.
-int combine_async(icerx_recutter *r, int n, int op, const uint8_t *d_data, size_t data_bytes, const uint64_t *d_offsets_a, size_t base_a,
-                  const uint64_t *d_lens_a, const uint64_t *d_offsets_b, size_t base_b, const uint64_t *d_lens_b, size_t stream_stride,
-                  uint8_t *d_out, size_t out_stride, uint64_t *d_sizes, int32_t *d_rcs, uint32_t *d_counts, void *workspace,
-                  size_t workspace_bytes, hipStream_t st)
+int combine_async(icerx_recutter *r, const RecutCall &c, int op, const CombineOperand &a, const CombineOperand &b, uint32_t *d_counts)
 {
     g_error.clear();
-    if (!r || n < 1 || n > kRecutMaxFrames || (op != kCombineUnion && op != kCombineDifference)) return ICER_INVALID_INPUT;
-    if (!d_data || !d_lens_a || !d_lens_b || !d_out || !d_sizes || !d_rcs || !d_counts || !workspace) return ICER_INVALID_INPUT;
-    if (data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", data_bytes);
-    const CombineLayout L = combine_layout(r, n, data_bytes);
-    if (workspace_bytes < L.total) return ICER_INVALID_INPUT;
+    if (!r || c.n < 1 || c.n > kRecutMaxFrames || (op != kCombineUnion && op != kCombineDifference)) return ICER_INVALID_INPUT;
+    if (!c.d_data || !a.lens || !b.lens || !c.d_out || !c.d_sizes || !c.d_rcs || !d_counts || !c.workspace) return ICER_INVALID_INPUT;
+    if (c.data_bytes >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", c.data_bytes);
+    const CombineLayout L = combine_layout(r, c.n, c.data_bytes);
+    if (c.workspace_bytes < L.total) return ICER_INVALID_INPUT;
     int rc = ICER_RESULT_OK;
-    uint8_t *ws = (uint8_t *)workspace;
-    uint64_t *foff = (uint64_t *)(ws + L.foff);
-    uint32_t *from = (uint32_t *)(ws + L.from), *bytes = (uint32_t *)(ws + L.bytes);
+    uint8_t *ws = (uint8_t *)c.workspace;
     const uint32_t n_units = r->red[0].n_units;
-    const CombineOperand a{d_offsets_a, d_lens_a, (uint64_t)base_a}, b{d_offsets_b, d_lens_b, (uint64_t)base_b};
+    const size_t tabs_a = (size_t)c.n * r->geom.slots();         // (A's packet tables: the first n; B's lie behind them)
+    const CombinePlan p{(uint64_t *)(ws + L.foff), (uint32_t *)(ws + L.from), (uint32_t *)(ws + L.bytes), d_counts};
+    const RecutOut o{c.d_out, c.out_stride, (unsigned long long *)c.d_sizes, c.d_rcs};
+    const RecutMasters ma{c.d_data, (uint32_t)c.data_bytes, a.offsets, a.lens, a.base, (uint64_t)c.stream_stride,
+                          (const DCandRec *)(ws + L.blob.cands), (const AsyncHead *)(ws + L.blob.head), r->geom, r->w, r->h,
+                          (uint32_t *)(ws + L.blob.tab_off), (uint32_t *)(ws + L.blob.tab_bits)};
+    RecutMasters mb = ma;
+    mb.offsets = b.offsets; mb.lens = b.lens; mb.base = b.base; mb.tab_off += tabs_a; mb.tab_bits += tabs_a;
 
     // 1. candidates over the blob
-    if ((rc = enqueue_blob_stage(L.blob, ws, 2u * (size_t)n, r->geom.slots(), d_data, data_bytes, (const uint32_t *)r->crc, r->n_cus, st)) !=
+    if ((rc = enqueue_blob_stage(L.blob, ws, 2u * (size_t)c.n, r->geom.slots(), c.d_data, c.data_bytes, (const uint32_t *)r->crc, r->n_cus, c.st)) !=
         ICER_RESULT_OK)
         return rc;
     // 2. per frame: both packet tables, the kept units and their places
-    ICER_LAUNCH_ON(st, combine_plan_kernel, (unsigned)n, kCombinePlanThreads, combine_plan_lds(kCombinePlanThreads), d_data,
-                   (uint32_t)data_bytes, op, a, b, (uint64_t)stream_stride, (const DCandRec *)(ws + L.blob.cands),
-                   (const AsyncHead *)(ws + L.blob.head), r->geom, r->w, r->h, (const uint32_t *)r->red[0].unit_slot,
-                   (const uint32_t *)r->red[0].final_order, n_units, (uint64_t)out_stride, (uint32_t *)(ws + L.blob.tab_off),
-                   (uint32_t *)(ws + L.blob.tab_bits), foff, from, bytes, (unsigned long long *)d_sizes, d_rcs, d_counts);
+    ICER_LAUNCH_ON(c.st, combine_plan_kernel, (unsigned)c.n, kCombinePlanThreads, combine_plan_lds(kCombinePlanThreads), ma, mb, op,
+                   (const uint32_t *)r->red[0].unit_slot, (const uint32_t *)r->red[0].final_order, n_units, p, o);
     HIP_TRY(hipGetLastError());
     // 3. the kept packets
-    ICER_LAUNCH_ON(st, combine_gather_kernel, dim3(n_units, (unsigned)n), kCombineGatherThreads, 0, d_data, n_units, (const uint64_t *)foff,
-                   (const uint32_t *)from, (const uint32_t *)bytes, d_out, out_stride);
+    ICER_LAUNCH_ON(c.st, combine_gather_kernel, dim3(n_units, (unsigned)c.n), kCombineGatherThreads, 0, c.d_data, n_units, (const uint64_t *)p.foff,
+                   (const uint32_t *)p.from, (const uint32_t *)p.bytes, c.d_out, c.out_stride);
     HIP_TRY(hipGetLastError());
 done:
     return rc;
@@ -169,8 +168,10 @@ int icerx_combine_device_async(icerx_recutter *r, int n, int op, const void *d_d
                                const uint64_t *d_lens_b, size_t stream_stride, uint8_t *d_out, size_t out_stride, uint64_t *d_sizes,
                                int32_t *d_rcs, uint32_t *d_counts, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    return combine_async(r, n, op, (const uint8_t *)d_data, data_bytes, d_offsets_a, base_a, d_lens_a, d_offsets_b, base_b, d_lens_b,
-                         stream_stride, d_out, out_stride, d_sizes, d_rcs, d_counts, d_workspace, workspace_bytes, (hipStream_t)stream);
+    const RecutCall c{n, (const uint8_t *)d_data, data_bytes, nullptr, stream_stride, nullptr, nullptr, nullptr, 0, d_out, out_stride, d_sizes, d_rcs,
+                      d_workspace, workspace_bytes, (hipStream_t)stream};
+    return combine_async(r, c, op, CombineOperand{d_offsets_a, d_lens_a, (uint64_t)base_a}, CombineOperand{d_offsets_b, d_lens_b, (uint64_t)base_b},
+                         d_counts);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@
 //   recut_scan_wave    one frame at one quota: scan_ladder_wave, or the frame's error (no offsets, size 0)
 //   copy_unit_recut    copy_unit_ladder for a source of any byte alignment (a packet inside a stored stream)
 // and, for cuts by resolution as well (icerx_recut_device_cuts_async), at the end of this file:
-//   recut_cut_status   a frame's status at reduce r
+//   recut_cut_status   a frame's status at reduce r, from what its walk left (RecutFrameHead)
 //   recut_cut_header   a kept packet's header as it stands in the derived stream at reduce r
 //   recut_offsets_by_master_unit   a cut's final offsets, from its geometry's unit order to the master's
 // Written with the SPMD macros of wave.hpp, so that tests/emu/recut_emu.cpp runs the same source on a CPU.
@@ -64,8 +64,8 @@ ICER_DEV void recut_scan_wave(int status, const uint32_t *bits, const uint32_t *
 // bytes behind a source word's builds its words from two of them (v_alignbyte) and stores them aligned; what is left at
 // both ends (fewer than 8 bytes each) goes byte by byte.  Nothing outside [src, src + len) is read, nothing outside a
 // destination's `len` bytes written.  Thread `tid` of `nth`.
-ICER_DEV void copy_unit_recut(const uint8_t *src, uint32_t len, const uint64_t *offs, size_t off_pitch, uint32_t n_q,
-                              uint8_t *out, size_t q_pitch, uint32_t tid, uint32_t nth)
+ICER_DEV void copy_unit_recut(const uint8_t *__restrict__ src, uint32_t len, const uint64_t *__restrict__ offs, size_t off_pitch, uint32_t n_q,
+                              uint8_t *__restrict__ out, size_t q_pitch, uint32_t tid, uint32_t nth)
 {
     const uint32_t sa = (uint32_t)((4u - ((uintptr_t)src & 3u)) & 3u);
     const uint32_t nfull = len > sa ? (len - sa) >> 2 : 0u;            // whole source words
@@ -105,10 +105,16 @@ ICER_HD int recut_cut_status(int status, uint32_t max_level, uint32_t reduce)
     if (status != kOk || reduce == 0u) return status;
     return max_level <= reduce ? kDecoderOutOfData : kOk;
 }
+// what a master's walk leaves of a frame (recut_walk, recut.hpp), and the head of every call's frame record
+struct RecutFrameHead {
+    int32_t status;
+    uint32_t max_level;
+};
+ICER_HD int recut_cut_status(const RecutFrameHead &f, uint32_t reduce) { return recut_cut_status(f.status, f.max_level, reduce); }
 
 // the 28 header bytes at `src` as they stand in the derived stream at reduce r -> dst: decomp_level - r, image_w and image_h
 // ceil(. / 2^r), the header CRC over the 24 bytes before it; r = 0: a copy.  Any alignment on both sides, one thread.
-ICER_HD void recut_cut_header(const uint32_t *crc_tab, const uint8_t *src, uint32_t reduce, uint8_t *dst)
+ICER_HD void recut_cut_header(const uint32_t *__restrict__ crc_tab, const uint8_t *__restrict__ src, uint32_t reduce, uint8_t *__restrict__ dst)
 {
     if (reduce == 0u) {
         for (uint32_t j = 0; j < (uint32_t)kHeaderBytes; j++) dst[j] = src[j];

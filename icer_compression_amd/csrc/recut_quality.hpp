@@ -9,13 +9,14 @@
 // 1/2^r size; its E rows are the master's, read through the family map of the recutter (recut_quality_build).
 //
 //   blob       enqueue_blob_stage
-//   frames     recut_quality_frame_kernel, one workgroup per frame: walk_frame and recut_unit_bits as recut_plan_kernel; the
-//              frame's record -- status, top level, LL means --; its sidecar row checked; the E rows of every geometry in use
-//              gathered through that geometry's family map
+//   frames     recut_quality_frame_kernel, one workgroup per frame: recut_frame_stage; the frame's record -- the walk's head,
+//              LL means --; its sidecar row checked; the E rows of every geometry in use gathered through that geometry's
+//              family map
 //   target     recut_target_scan_kernel, one wavefront per (frame, cut): scan_target_wave
 //   budget     recut_budget_curve_kernel, one wavefront per frame: curve_frame_wave; recut_budget_search_kernel, one workgroup
 //              per budget: budget_search_wave (state in the workspace), then budget_finish_wave, a wavefront a frame
 //   packets    recut_gather_kernel
+// Both calls run through one driver, recut_quality_async, on recut.hpp's RecutCall and RecutRun.
 // The unit tables of a recutter have cap_is_bound 0 and no bit count is kUnitFailed: the wave functions' redo flags are 0.
 #include "budget_core.hpp"
 #include "subband_gain.hpp"
@@ -28,11 +29,11 @@ constexpr uint32_t kRecutQualityScanThreads = 1, kRecutBudgetThreads = 1;
 constexpr uint32_t kRecutQualityScanThreads = 64, kRecutBudgetThreads = 64 * 16;
 #endif
 
-// what the frame stage leaves of a frame: the walk's status and top level (recut_cut_status), whether its sidecar row is
-// unusable, its LL means as scan_target_wave reads them
+// what the frame stage leaves of a frame: the walk's, whether its sidecar row is unusable, its LL means as scan_target_wave
+// reads them
 struct RecutQualityFrame {
-    int32_t status;
-    uint32_t max_level, bad_sidecar, pad;
+    RecutFrameHead head;
+    uint32_t bad_sidecar, pad;
     uint16_t means[4];
 };
 
@@ -46,16 +47,27 @@ struct RecutQualityTables {
 
 ICER_HD int recut_quality_status(const RecutQualityFrame &f, uint32_t reduce)
 {
-    const int s = recut_cut_status(f.status, f.max_level, reduce);
+    const int s = recut_cut_status(f.head, reduce);
     return s != kOk ? s : f.bad_sidecar ? kInvalidInput : kOk;
 }
 
 // The cuts call's workspace, then: a record per frame, the gathered E rows (every geometry's, a frame after the other), and
 // for the budget call the frames' curves (pitch: units of the full geometry + 1), their heads and a search state per budget
-// and frame.
+// and frame.  RecutQualityWork: the same as pointers, by value with the launches; RecutQualityOut: the outputs of both calls.
 struct RecutQualityLayout {
     RecutLayout cut;
     size_t frames, energy, curve_d, curve_used, head, state, total;
+};
+struct RecutQualityWork {
+    RecutQualityFrame *frames;
+    unsigned long long *energy, *curve_d, *curve_used;
+    uint32_t *head, pitch;
+    BudgetState *state;
+};
+struct RecutQualityOut {
+    RecutOut cut;
+    int32_t *flag;                                    // reached / at_cap
+    unsigned long long *dist, *equiv, *threshold, *total;
 };
 RecutQualityLayout recut_quality_layout(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts, bool budget)
 {
@@ -77,34 +89,23 @@ RecutQualityLayout recut_quality_layout(const icerx_recutter *r, int n, size_t d
     return L;
 }
 
-// one workgroup per frame, as recut_plan_kernel up to its first barrier; then the frame's sidecar row sidecar[k * stride ..]:
-// the means word into the record; every row of E checked -- non-decreasing in b, E[g][P] at most fam_cap[g] --; and for every
-// geometry in use at which the frame has a stream, its families' rows through fam_map (r = 0: as they are) into `energy`.
-// A row that fails the check is still gathered: nothing reads it, the frame has a status.
+// one workgroup per frame: recut_frame_stage; then the frame's sidecar row sidecar[k * stride ..]: the means word into the
+// record; every row of E checked -- non-decreasing in b, E[g][P] at most fam_cap[g] --; and for every geometry in use at which
+// the frame has a stream, its families' rows through fam_map (r = 0: as they are) into `energy`.  A row that fails the check
+// is still gathered: nothing reads it, the frame has a status.
 __global__ void __launch_bounds__(256)
-recut_quality_frame_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, const uint64_t *__restrict__ offsets, uint64_t stream_stride,
-                           const uint64_t *__restrict__ lens, const DCandRec *__restrict__ recs, const AsyncHead *__restrict__ head,
-                           DPlanGeom geom, uint64_t image_w, uint64_t image_h, RecutCutTables tabs, uint32_t bits_stride, uint32_t used,
-                           RecutQualityTables q, const unsigned long long *__restrict__ sidecar, size_t sidecar_stride,
-                           uint32_t *__restrict__ tab_off, uint32_t *__restrict__ tab_bits, uint32_t *__restrict__ unit_bits,
-                           RecutQualityFrame *__restrict__ frames, unsigned long long *__restrict__ energy)
+recut_quality_frame_kernel(RecutMasters m, RecutCutTables tabs, RecutWork w, uint32_t used, RecutQualityTables q,
+                           const unsigned long long *__restrict__ sidecar, size_t sidecar_stride, RecutQualityWork qw)
 {
     ICER_DYNAMIC_LDS(uint8_t, lds);                            // kWalkLds
     const uint32_t k = blockIdx.x, tid = threadIdx.x, nth = blockDim.x;
-    const uint64_t off = offsets ? offsets[k] : (uint64_t)k * stream_stride, len = lens[k];
-    uint32_t *to = tab_off + (size_t)k * geom.slots(), *tb = tab_bits + (size_t)k * geom.slots();
-    uint32_t *bits = unit_bits + (size_t)k * bits_stride;
-    WalkNotes notes;
-    const DWalk s = walk_frame(lds, blob, blob_len, off, len, recs, head, geom, image_w, image_h, to, tb, &notes);
-    const int status = recut_frame_status(notes.inside != 0u, s.cursor, notes.other_size != 0u);
-    for (uint32_t r = 0; r <= (uint32_t)kRecutMaxReduce; r++)
-        if (((used >> r) & 1u) && recut_cut_status(status, notes.max_level, r) == kOk)
-            recut_unit_bits(to, tb, tabs.unit_slot[r], tabs.n_units[r], bits + tabs.bits_at[r], tid, nth);
+    const RecutFrameHead head = recut_frame_stage(lds, m, k, tabs, w, used, tid, nth);
+    RecutQualityFrame *frames = qw.frames;
     const uint32_t row_len = q.P + 1u, n_fam = q.n_families[0];
     const unsigned long long *E = sidecar + (size_t)k * sidecar_stride;
     if (tid == 0) {
         RecutQualityFrame f;
-        f.status = status; f.max_level = notes.max_level; f.bad_sidecar = 0u; f.pad = 0u;
+        f.head = head; f.bad_sidecar = 0u; f.pad = 0u;
         const unsigned long long word = E[(size_t)n_fam * row_len];
         for (uint32_t c = 0; c < 4u; c++) f.means[c] = (uint16_t)(word >> (16u * c));
         frames[k] = f;
@@ -116,9 +117,9 @@ recut_quality_frame_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, 
         for (uint32_t b = 0; b < q.P; b++) bad |= e[b] > e[b + 1u];
         if (bad) frames[k].bad_sidecar = 1u;                    // (every thread that writes writes the same)
     }
-    unsigned long long *out = energy + (size_t)k * q.e_stride;
+    unsigned long long *out = qw.energy + (size_t)k * q.e_stride;
     for (uint32_t r = 0; r <= (uint32_t)kRecutMaxReduce; r++) {
-        if (!((used >> r) & 1u) || recut_cut_status(status, notes.max_level, r) != kOk) continue;
+        if (!((used >> r) & 1u) || recut_cut_status(head, r) != kOk) continue;
         const uint32_t *map = tabs.full_to_cut[r] ? q.fam_map[r] : nullptr;
         for (uint32_t i = tid; i < q.n_families[r] * row_len; i += nth) {
             const uint32_t g = i / row_len, b = i - g * row_len;
@@ -131,44 +132,38 @@ recut_quality_frame_kernel(const uint8_t *__restrict__ blob, uint32_t blob_len, 
 // call's byte cap.  Rows c * n + k as recut_plan_kernel's.  A frame with a status is a frame without a stream: what
 // recut_scan_wave writes, reached 0, dist 0, equiv the cap.
 __global__ void __launch_bounds__(64)
-recut_target_scan_kernel(RecutCutTables tabs, uint32_t bits_stride, RecutCuts cuts, TargetList targets, uint64_t byte_cap, RecutQualityTables q,
-                         const RecutQualityFrame *__restrict__ frames, const uint32_t *__restrict__ unit_bits,
-                         const unsigned long long *__restrict__ energy, uint64_t *foff, uint64_t *by_unit,
-                         unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs, int32_t *__restrict__ reached,
-                         unsigned long long *__restrict__ dist, unsigned long long *__restrict__ equiv)
+recut_target_scan_kernel(RecutCutTables tabs, RecutWork w, RecutCuts cuts, TargetList targets, uint64_t byte_cap, RecutQualityTables q,
+                         RecutQualityWork qw, RecutQualityOut o)
 {
-    const uint32_t k = blockIdx.x, c = blockIdx.y, n = gridDim.x, tid = threadIdx.x, n_full = tabs.n_units[0];
+    const uint32_t k = blockIdx.x, c = blockIdx.y, n = gridDim.x, tid = threadIdx.x;
     const uint32_t r = cuts.reduce[c];
     const size_t row = (size_t)c * n + k;
-    const RecutQualityFrame &fr = frames[k];
+    const RecutQualityFrame &fr = qw.frames[k];
     const int status = recut_quality_status(fr, r);
-    const uint32_t *bits = unit_bits + (size_t)k * bits_stride + tabs.bits_at[r];
-    uint64_t *cut_off = (r ? by_unit : foff) + row * n_full;
+    const uint32_t *bits = w.bits(k) + tabs.bits_at[r];
+    uint64_t *cut_off = w.cut_row(r, row);
     if (status != kOk) {
-        recut_scan_wave(status, bits, tabs.final_order[r], tabs.n_units[r], byte_cap, tabs.units[r], cut_off, sizes + row, rcs + row);
-        if (tid == 0) { reached[row] = 0; dist[row] = 0; equiv[row] = byte_cap; }
+        recut_scan_wave(status, bits, tabs.final_order[r], tabs.n_units[r], byte_cap, tabs.units[r], cut_off, o.cut.sizes + row, o.cut.rcs + row);
+        if (tid == 0) { o.flag[row] = 0; o.dist[row] = 0; o.equiv[row] = byte_cap; }
     } else
         (void)scan_target_wave(bits, tabs.final_order[r], tabs.n_units[r], targets.t[c], byte_cap, 0, tabs.units[r],
-                               energy + (size_t)k * q.e_stride + q.e_at[r], q.weight[r], q.n_families[r], q.P, q.ll_term[r], q.chan[r],
-                               fr.means, cut_off, sizes + row, rcs + row, reached + row, dist + row, equiv + row);
+                               qw.energy + (size_t)k * q.e_stride + q.e_at[r], q.weight[r], q.n_families[r], q.P, q.ll_term[r], q.chan[r],
+                               fr.means, cut_off, o.cut.sizes + row, o.cut.rcs + row, o.flag + row, o.dist + row, o.equiv + row);
     if (r) {
         ICER_BARRIER();
-        recut_offsets_by_master_unit(cut_off, tabs.full_to_cut[r], n_full, foff + row * n_full, tid, blockDim.x);
+        recut_row_by_master(w, tabs, r, row, tid, blockDim.x);
     }
 }
 
 // one wavefront per frame: its curve at reduce r under the byte cap (curve_frame_wave); a frame with a status is a skipped one
 __global__ void __launch_bounds__(64)
-recut_budget_curve_kernel(RecutCutTables tabs, uint32_t bits_stride, uint32_t r, uint64_t byte_cap, RecutQualityTables q,
-                          const RecutQualityFrame *__restrict__ frames, const uint32_t *__restrict__ unit_bits,
-                          const unsigned long long *__restrict__ energy, uint32_t pitch, unsigned long long *__restrict__ curve_d,
-                          unsigned long long *__restrict__ curve_used, uint32_t *__restrict__ head)
+recut_budget_curve_kernel(RecutCutTables tabs, RecutWork w, uint32_t r, uint64_t byte_cap, RecutQualityTables q, RecutQualityWork qw)
 {
     const uint32_t k = blockIdx.x;
-    const RecutQualityFrame &fr = frames[k];
-    curve_frame_wave(unit_bits + (size_t)k * bits_stride + tabs.bits_at[r], tabs.n_units[r], byte_cap, recut_quality_status(fr, r) != kOk,
-                     tabs.units[r], energy + (size_t)k * q.e_stride + q.e_at[r], q.weight[r], q.n_families[r], q.P, q.ll_term[r], q.chan[r],
-                     fr.means, curve_d + (size_t)k * pitch, curve_used + (size_t)k * pitch, head + (size_t)k * kCurveHeadWords);
+    const RecutQualityFrame &fr = qw.frames[k];
+    curve_frame_wave(w.bits(k) + tabs.bits_at[r], tabs.n_units[r], byte_cap, recut_quality_status(fr, r) != kOk, tabs.units[r],
+                     qw.energy + (size_t)k * q.e_stride + q.e_at[r], q.weight[r], q.n_families[r], q.P, q.ll_term[r], q.chan[r], fr.means,
+                     qw.curve_d + (size_t)k * qw.pitch, qw.curve_used + (size_t)k * qw.pitch, qw.head + (size_t)k * kCurveHeadWords);
 }
 
 // one workgroup per budget over all frames of the call: wavefront 0 finds the common threshold and hands out what it leaves
@@ -176,41 +171,33 @@ recut_budget_curve_kernel(RecutCutTables tabs, uint32_t bits_stride, uint32_t r,
 // (budget_finish_wave; a frame with a status: as in recut_target_scan_kernel), and the workgroup turns the final offsets of a
 // cut at r > 0 into the order of the master's units.  Rows b * n + k.
 __global__ void __launch_bounds__(64 * 16)
-recut_budget_search_kernel(RecutCutTables tabs, uint32_t bits_stride, uint32_t r, BudgetList budgets, uint64_t byte_cap, uint32_t n,
-                           const RecutQualityFrame *__restrict__ frames, const uint32_t *__restrict__ unit_bits, uint32_t pitch,
-                           const unsigned long long *__restrict__ curve_d, const unsigned long long *__restrict__ curve_used,
-                           const uint32_t *__restrict__ head, BudgetState *state, uint64_t *foff, uint64_t *by_unit,
-                           unsigned long long *__restrict__ sizes, int32_t *__restrict__ rcs, int32_t *__restrict__ at_cap,
-                           unsigned long long *__restrict__ dist, unsigned long long *__restrict__ equiv,
-                           unsigned long long *__restrict__ threshold, unsigned long long *__restrict__ total)
+recut_budget_search_kernel(RecutCutTables tabs, RecutWork w, uint32_t r, BudgetList budgets, uint64_t byte_cap, uint32_t n, RecutQualityWork qw,
+                           RecutQualityOut o)
 {
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, n_full = tabs.n_units[0];
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
 #ifdef ICER_HOST_MOCK
     const uint32_t wave = 0, waves = 1, lane0 = 1;
 #else
     const uint32_t wave = tid >> 6, waves = blockDim.x >> 6, lane0 = (tid & 63u) == 0u;
 #endif
-    BudgetState *st = state + (size_t)b * n;
-    if (wave == 0) budget_search_wave(curve_d, curve_used, head, pitch, n, budgets.b[b], st, threshold + b, total + b);
+    BudgetState *st = qw.state + (size_t)b * n;
+    if (wave == 0) budget_search_wave(qw.curve_d, qw.curve_used, qw.head, qw.pitch, n, budgets.b[b], st, o.threshold + b, o.total + b);
     ICER_BARRIER();
     for (uint32_t k = wave; k < n; k += waves) {
         const size_t row = (size_t)b * n + k;
-        const int status = recut_quality_status(frames[k], r);
-        const uint32_t *bits = unit_bits + (size_t)k * bits_stride + tabs.bits_at[r];
-        uint64_t *cut_off = (r ? by_unit : foff) + row * n_full;
+        const int status = recut_quality_status(qw.frames[k], r);
+        const uint32_t *bits = w.bits(k) + tabs.bits_at[r];
+        uint64_t *cut_off = w.cut_row(r, row);
         if (status != kOk) {
-            recut_scan_wave(status, bits, tabs.final_order[r], tabs.n_units[r], byte_cap, tabs.units[r], cut_off, sizes + row, rcs + row);
-            if (lane0) { at_cap[row] = 0; dist[row] = 0; equiv[row] = byte_cap; }
+            recut_scan_wave(status, bits, tabs.final_order[r], tabs.n_units[r], byte_cap, tabs.units[r], cut_off, o.cut.sizes + row, o.cut.rcs + row);
+            if (lane0) { o.flag[row] = 0; o.dist[row] = 0; o.equiv[row] = byte_cap; }
         } else
-            (void)budget_finish_wave(bits, tabs.final_order[r], tabs.n_units[r], st[k].lo, head[(size_t)k * kCurveHeadWords], st[k].d_lo, byte_cap, 0,
-                                     tabs.units[r], cut_off, sizes + row, rcs + row, at_cap + row, dist + row, equiv + row);
+            (void)budget_finish_wave(bits, tabs.final_order[r], tabs.n_units[r], st[k].lo, qw.head[(size_t)k * kCurveHeadWords], st[k].d_lo, byte_cap,
+                                     0, tabs.units[r], cut_off, o.cut.sizes + row, o.cut.rcs + row, o.flag + row, o.dist + row, o.equiv + row);
     }
     if (r) {
         ICER_BARRIER();
-        for (uint32_t k = 0; k < n; k++) {
-            const size_t row = (size_t)b * n + k;
-            recut_offsets_by_master_unit(by_unit + row * n_full, tabs.full_to_cut[r], n_full, foff + row * n_full, tid, blockDim.x);
-        }
+        for (uint32_t k = 0; k < n; k++) recut_row_by_master(w, tabs, r, (size_t)b * n + k, tid, blockDim.x);
     }
 }
 
@@ -286,12 +273,12 @@ int recut_quality_upload(icerx_recutter *r, const RecutQualityHost &q)
         icerx_recutter::Quality &g = r->qual[k];
         g.n_families = (uint32_t)q.weight[k].size();
         r->families_total += g.n_families;
-        HIP_TRY(recut_upload(&g.weight, q.weight[k].data(), sizeof(uint32_t) * g.n_families));
-        HIP_TRY(recut_upload(&g.chan, q.chan[k].data(), sizeof(uint32_t) * g.n_families));
-        HIP_TRY(recut_upload(&g.ll_term, q.ll_term[k].data(), sizeof(unsigned long long) * g.n_families));
-        if (k) HIP_TRY(recut_upload(&g.fam_map, q.fam_map[k].data(), sizeof(uint32_t) * g.n_families));
+        HIP_TRY(recut_upload(r, &g.weight, q.weight[k].data(), sizeof(uint32_t) * g.n_families));
+        HIP_TRY(recut_upload(r, &g.chan, q.chan[k].data(), sizeof(uint32_t) * g.n_families));
+        HIP_TRY(recut_upload(r, &g.ll_term, q.ll_term[k].data(), sizeof(unsigned long long) * g.n_families));
+        if (k) HIP_TRY(recut_upload(r, &g.fam_map, q.fam_map[k].data(), sizeof(uint32_t) * g.n_families));
     }
-    HIP_TRY(recut_upload(&r->fam_cap, q.fam_cap.data(), sizeof(unsigned long long) * q.fam_cap.size()));
+    HIP_TRY(recut_upload(r, &r->fam_cap, q.fam_cap.data(), sizeof(unsigned long long) * q.fam_cap.size()));
 done:
     return rc;
 }
@@ -328,91 +315,57 @@ bool recut_target_threshold(const icerx_recutter *r, double target_mse, int redu
     return true;
 }
 
-// Both calls: `reduces` and the thresholds or budgets are the call's cuts.  Every check before the first launch.
-struct RecutQualityCall {
-    int n;
-    const uint8_t *d_data;
-    size_t data_bytes;
-    const uint64_t *d_offsets;
-    size_t stream_stride;
-    const uint64_t *d_lens, *d_sidecar;
-    size_t sidecar_stride;
-    int n_cuts;
-    size_t byte_cap;
-    uint8_t *d_out;
-    size_t out_stride;
-    uint64_t *d_sizes;
-    int32_t *d_rcs, *d_flag;                           // reached / at_cap
-    uint64_t *d_dist, *d_equiv;
-    void *workspace;
-    size_t workspace_bytes;
-    hipStream_t st;
+// what the two calls have beyond a RecutCall: the sidecars, the byte cap, their own outputs (d_threshold / d_total: the budget call's)
+struct RecutQualityArgs {
+    const uint64_t *d_sidecar;
+    size_t sidecar_stride, byte_cap;
+    int32_t *d_flag;                                  // reached / at_cap
+    uint64_t *d_dist, *d_equiv, *d_threshold, *d_total;
 };
 
-int recut_quality_async(icerx_recutter *r, const RecutQualityCall &c, const int *reduces, const TargetList *targets, const BudgetList *budgets,
-                        uint64_t *d_threshold, uint64_t *d_total)
+// Both calls: the call's reduces and the thresholds or budgets are its cuts, the byte cap every cut's quota.  Every check
+// before the first launch.
+int recut_quality_async(icerx_recutter *r, const RecutCall &call, const RecutQualityArgs &a, const TargetList *targets, const BudgetList *budgets)
 {
-    if (!r || r->filt < 0 || !c.d_sidecar || !c.d_flag || !c.d_dist || !c.d_equiv) return ICER_INVALID_INPUT;
-    if (c.n_cuts < 1 || c.n_cuts > kMaxLadder) return ICER_INVALID_INPUT;
-    if (c.sidecar_stride < recut_sidecar_entries(r)) return ICER_INVALID_INPUT;
+    if (!r || r->filt < 0 || !a.d_sidecar || !a.d_flag || !a.d_dist || !a.d_equiv) return ICER_INVALID_INPUT;
+    if (call.n_cuts < 1 || call.n_cuts > kMaxLadder) return ICER_INVALID_INPUT;
+    if (a.sidecar_stride < recut_sidecar_entries(r)) return ICER_INVALID_INPUT;
     size_t caps[kMaxLadder];
-    for (int k = 0; k < c.n_cuts; k++) caps[k] = c.byte_cap;
-    RecutCuts cuts = {};
-    uint32_t used = 0;
-    int rc = recut_check(r, c.n, c.d_data, c.data_bytes, c.d_lens, reduces, caps, c.n_cuts, c.d_out, c.out_stride, c.d_sizes, c.d_rcs, c.workspace,
-                         &cuts, &used);
+    for (int k = 0; k < call.n_cuts; k++) caps[k] = a.byte_cap;
+    RecutCall c = call;
+    c.quotas = caps;
+    RecutRun run;
+    int rc = recut_check(r, c, &run);
     if (rc != ICER_RESULT_OK) return rc;
     const RecutQualityLayout L = recut_quality_layout(r, c.n, c.data_bytes, c.n_cuts, budgets != nullptr);
-    if (c.workspace_bytes < L.total) return ICER_INVALID_INPUT;
+    if ((rc = recut_begin(r, c, L.cut, L.total, &run)) != ICER_RESULT_OK) return rc;
     uint8_t *ws = (uint8_t *)c.workspace;
-    uint32_t *tab_off = (uint32_t *)(ws + L.cut.blob.tab_off), *tab_bits = (uint32_t *)(ws + L.cut.blob.tab_bits);
-    uint32_t *unit_bits = (uint32_t *)(ws + L.cut.bits);
-    uint64_t *foff = (uint64_t *)(ws + L.cut.foff), *by_unit = (uint64_t *)(ws + L.cut.by_unit);
-    RecutQualityFrame *frames = (RecutQualityFrame *)(ws + L.frames);
-    unsigned long long *energy = (unsigned long long *)(ws + L.energy);
-    const uint32_t n_full = r->red[0].n_units, n = (uint32_t)c.n;
-    const RecutCutTables tabs = recut_cut_tables(r);
+    const uint32_t n = (uint32_t)c.n, reduce = run.cuts.reduce[0];
+    const RecutQualityWork qw{(RecutQualityFrame *)(ws + L.frames), (unsigned long long *)(ws + L.energy), (unsigned long long *)(ws + L.curve_d),
+                              (unsigned long long *)(ws + L.curve_used), (uint32_t *)(ws + L.head), run.work.n_full + 1u,
+                              (BudgetState *)(ws + L.state)};
+    const RecutQualityOut o{run.out, a.d_flag, (unsigned long long *)a.d_dist, (unsigned long long *)a.d_equiv,
+                            (unsigned long long *)a.d_threshold, (unsigned long long *)a.d_total};
     const RecutQualityTables q = recut_quality_tables(r);
 
-    // 1. candidates over the blob
-    if ((rc = enqueue_blob_stage(L.cut.blob, ws, (size_t)n, r->geom.slots(), c.d_data, c.data_bytes, (const uint32_t *)r->crc, r->n_cus, c.st)) !=
-        ICER_RESULT_OK)
-        return rc;
-    // 2. per frame: packet table, bit counts, the sidecar row checked and gathered
-    ICER_LAUNCH_ON(c.st, recut_quality_frame_kernel, n, kRecutPlanThreads, kWalkLds, c.d_data, (uint32_t)c.data_bytes, c.d_offsets,
-                   (uint64_t)c.stream_stride, c.d_lens, (const DCandRec *)(ws + L.cut.blob.cands), (const AsyncHead *)(ws + L.cut.blob.head), r->geom,
-                   r->w, r->h, tabs, L.cut.bits_stride, used, q, (const unsigned long long *)c.d_sidecar, c.sidecar_stride, tab_off, tab_bits,
-                   unit_bits, frames, energy);
+    // per frame: packet table, bit counts, the sidecar row checked and gathered
+    ICER_LAUNCH_ON(c.st, recut_quality_frame_kernel, n, kRecutPlanThreads, kWalkLds, run.masters, run.tabs, run.work, run.used, q,
+                   (const unsigned long long *)a.d_sidecar, a.sidecar_stride, qw);
     HIP_TRY(hipGetLastError());
     if (targets) {
-        // 3. per frame and cut: the walk to the cut's threshold
-        ICER_LAUNCH_ON(c.st, recut_target_scan_kernel, dim3(n, (unsigned)c.n_cuts), kRecutQualityScanThreads, 0, tabs, L.cut.bits_stride, cuts,
-                       *targets, (uint64_t)c.byte_cap, q, (const RecutQualityFrame *)frames, (const uint32_t *)unit_bits,
-                       (const unsigned long long *)energy, foff, by_unit, (unsigned long long *)c.d_sizes, c.d_rcs, c.d_flag,
-                       (unsigned long long *)c.d_dist, (unsigned long long *)c.d_equiv);
+        // per frame and cut: the walk to the cut's threshold
+        ICER_LAUNCH_ON(c.st, recut_target_scan_kernel, dim3(n, (unsigned)c.n_cuts), kRecutQualityScanThreads, 0, run.tabs, run.work, run.cuts,
+                       *targets, (uint64_t)a.byte_cap, q, qw, o);
         HIP_TRY(hipGetLastError());
     } else {
-        // 3. per frame: its curve; per budget: the common threshold, the fill, every frame's cut
-        const uint32_t pitch = n_full + 1u, reduce = cuts.reduce[0];
-        unsigned long long *curve_d = (unsigned long long *)(ws + L.curve_d), *curve_used = (unsigned long long *)(ws + L.curve_used);
-        uint32_t *head = (uint32_t *)(ws + L.head);
-        ICER_LAUNCH_ON(c.st, recut_budget_curve_kernel, n, kRecutQualityScanThreads, 0, tabs, L.cut.bits_stride, reduce, (uint64_t)c.byte_cap, q,
-                       (const RecutQualityFrame *)frames, (const uint32_t *)unit_bits, (const unsigned long long *)energy, pitch, curve_d,
-                       curve_used, head);
+        // per frame: its curve; per budget: the common threshold, the fill, every frame's cut
+        ICER_LAUNCH_ON(c.st, recut_budget_curve_kernel, n, kRecutQualityScanThreads, 0, run.tabs, run.work, reduce, (uint64_t)a.byte_cap, q, qw);
         HIP_TRY(hipGetLastError());
-        ICER_LAUNCH_ON(c.st, recut_budget_search_kernel, (unsigned)c.n_cuts, kRecutBudgetThreads, 0, tabs, L.cut.bits_stride, reduce, *budgets,
-                       (uint64_t)c.byte_cap, n, (const RecutQualityFrame *)frames, (const uint32_t *)unit_bits, pitch,
-                       (const unsigned long long *)curve_d, (const unsigned long long *)curve_used, (const uint32_t *)head,
-                       (BudgetState *)(ws + L.state), foff, by_unit, (unsigned long long *)c.d_sizes, c.d_rcs, c.d_flag,
-                       (unsigned long long *)c.d_dist, (unsigned long long *)c.d_equiv, (unsigned long long *)d_threshold,
-                       (unsigned long long *)d_total);
+        ICER_LAUNCH_ON(c.st, recut_budget_search_kernel, (unsigned)c.n_cuts, kRecutBudgetThreads, 0, run.tabs, run.work, reduce, *budgets,
+                       (uint64_t)a.byte_cap, n, qw, o);
         HIP_TRY(hipGetLastError());
     }
-    // 4. the kept packets, each with its cut's header
-    ICER_LAUNCH_ON(c.st, recut_gather_kernel, dim3(n_full, n), kRecutGatherThreads, 0, c.d_data, c.d_offsets, (uint64_t)c.stream_stride, r->geom,
-                   (const uint32_t *)r->red[0].unit_slot, n_full, tab_off, tab_bits, foff, cuts, (uint32_t)c.n_cuts, (const uint32_t *)r->crc,
-                   c.d_out, c.out_stride);
-    HIP_TRY(hipGetLastError());
+    rc = recut_finish(run);
 done:
     return rc;
 }
@@ -424,7 +377,7 @@ extern "C" {
 int icerx_recutter_create_quality(icerx_recutter **out, int device, size_t w, size_t h, int channels, int stages, int filt, unsigned segments,
                                   int sample_bits, int max_reduce)
 {
-    return recutter_create(out, device, w, h, channels, stages, segments, sample_bits, max_reduce, true, filt);
+    return recutter_create(out, w, h, channels, stages, segments, sample_bits, RecutterOptions{device, max_reduce, true, filt});
 }
 
 size_t icerx_recut_sidecar_entries(const icerx_recutter *r) { return recut_sidecar_entries(r); }
@@ -437,8 +390,7 @@ uint64_t icerx_recut_target_threshold(const icerx_recutter *r, double target_mse
 
 size_t icerx_recut_target_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_cuts)
 {
-    if (!r || r->filt < 0 || n <= 0 || n_cuts < 1 || n_cuts > kMaxLadder) return 0;
-    return recut_quality_layout(r, n, data_bytes, n_cuts, false).total;
+    return recut_sizable(r, n, n_cuts, true) ? recut_quality_layout(r, n, data_bytes, n_cuts, false).total : 0;
 }
 
 int icerx_recut_device_target_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
@@ -454,15 +406,15 @@ int icerx_recut_device_target_async(icerx_recutter *r, int n, const void *d_data
         const int reduce = reduces ? reduces[c] : 0;
         if (reduce < 0 || reduce > r->max_reduce || !recut_target_threshold(r, target_mse[c], reduce, &targets.t[c])) return ICER_INVALID_INPUT;
     }
-    const RecutQualityCall c{n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, d_sidecar, sidecar_stride, n_cuts, byte_cap,
-                             d_out, out_stride, d_sizes, d_rcs, d_reached, d_dist, d_equiv_quota, d_workspace, workspace_bytes, (hipStream_t)stream};
-    return recut_quality_async(r, c, reduces, &targets, nullptr, nullptr, nullptr);
+    const RecutCall c{n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, reduces, nullptr, n_cuts, d_out, out_stride, d_sizes,
+                      d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream};
+    const RecutQualityArgs a{d_sidecar, sidecar_stride, byte_cap, d_reached, d_dist, d_equiv_quota, nullptr, nullptr};
+    return recut_quality_async(r, c, a, &targets, nullptr);
 }
 
 size_t icerx_recut_budget_workspace_bytes(const icerx_recutter *r, int n, size_t data_bytes, int n_budgets)
 {
-    if (!r || r->filt < 0 || n <= 0 || n_budgets < 1 || n_budgets > kMaxLadder) return 0;
-    return recut_quality_layout(r, n, data_bytes, n_budgets, true).total;
+    return recut_sizable(r, n, n_budgets, true) ? recut_quality_layout(r, n, data_bytes, n_budgets, true).total : 0;
 }
 
 int icerx_recut_device_budget_async(icerx_recutter *r, int n, const void *d_data, size_t data_bytes, const uint64_t *d_offsets,
@@ -476,9 +428,10 @@ int icerx_recut_device_budget_async(icerx_recutter *r, int n, const void *d_data
     BudgetList list = {};
     int reduces[kMaxLadder];
     for (int b = 0; b < n_budgets; b++) { list.b[b] = budgets[b]; reduces[b] = reduce; }
-    const RecutQualityCall c{n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, d_sidecar, sidecar_stride, n_budgets, byte_cap,
-                             d_out, out_stride, d_sizes, d_rcs, d_at_cap, d_dist, d_equiv_quota, d_workspace, workspace_bytes, (hipStream_t)stream};
-    return recut_quality_async(r, c, reduces, nullptr, &list, d_threshold, d_total);
+    const RecutCall c{n, (const uint8_t *)d_data, data_bytes, d_offsets, stream_stride, d_lens, reduces, nullptr, n_budgets, d_out, out_stride,
+                      d_sizes, d_rcs, d_workspace, workspace_bytes, (hipStream_t)stream};
+    const RecutQualityArgs a{d_sidecar, sidecar_stride, byte_cap, d_at_cap, d_dist, d_equiv_quota, d_threshold, d_total};
+    return recut_quality_async(r, c, a, nullptr, &list);
 }
 
 }  // extern "C"
