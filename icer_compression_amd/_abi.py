@@ -87,6 +87,7 @@ _cut_out = [p, sz, p, p]                                         # out, its stri
 _work = [p, sz, p]                                               # workspace, its bytes, stream
 _sync_win = [p, i, p, szp, szp, p, p, sz, sz, ip, szp, szp, p]   # the synchronous window calls (icer_hip_dec_window.h)
 _async_win = [p, i, p, sz, p, sz, p, p, p, sz, sz, p, p, p, p] + _work
+_feed = [p, i, ip, p, szp, szp, p, ip, szp, szp]                 # session, n, slots, data, offsets, lens, out, rcs, ws, hs
 
 DECODER = {
     "icer_get_image_dimensions": (i, [u8p, sz, szp, szp]),
@@ -147,6 +148,15 @@ DECODER = {
     "icerx_decode_window_display_workspace_bytes": (sz, [p, i, sz, sz]),
     "icerx_decode_device_window_display_async": (i, _async_win),
     "icerx_decompress_window": (i, [handle, i, szp, szp, sz, u8p, sz, i, i, u, i, i, i, p, p]),
+    # progressive decode sessions: held frames refined from new packets (include/icer_hip_dec_session.h)
+    "icerx_session_create": (i, [handle, p, i, sz]),
+    "icerx_session_destroy": (None, [p]),
+    "icerx_session_reset": (i, [p, i]),
+    "icerx_session_feed_host": (i, _feed),
+    "icerx_session_feed_device": (i, _feed),
+    "icerx_session_feed_device_display": (i, _feed),
+    "icerx_session_planes_held": (i, [p, i, i, i, i, i]),
+    "icerx_session_stats": (i, [p, C.POINTER(u64)]),
     "icerx_decoder_last_error": (text, []),
     **_wavelets("icer_inverse_wavelet_transform"),
     "icer_from_sign_magnitude_int16": (None, [p, sz]),

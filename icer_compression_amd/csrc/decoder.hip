@@ -722,6 +722,7 @@ int decompress_planes(void *const planes[], int channels, size_t *image_w, size_
 }  // namespace
 
 #include "decoder_window.hpp"          // the window decode: decode_window_batch, and what decode_async enqueues for a window call
+#include "decoder_session.hpp"         // progressive decode sessions: icerx_session_* (include/icer_hip_dec_session.h)
 #ifdef ICER_DECODE_ASYNC
 #include "decoder_async.hpp"
 #include "recut.hpp"                   // icerx_recut_device_async: stored streams re-cut to smaller byte quotas

@@ -34,6 +34,9 @@ namespace icer {
 constexpr int kDecoderOutOfData = -7;      // ICER_DECODER_OUT_OF_DATA, icer.h:100
 constexpr int kDecodedInvalidData = -8;    // ICER_DECODED_INVALID_DATA, icer.h:101
 constexpr uint32_t kNoPacket = 0xFFFFFFFFu;
+// ChainDesc::pkt of a plane that a decode session (decoder_session.hpp) holds already: its bits are in the state plane, there
+// is no packet to run.  Not kNoPacket: whoever counts a chain's planes from the top (reconstruct_kernel) counts it.
+constexpr uint32_t kHeldPlane = 0xFFFFFFFEu;
 
 // tables of the entropy decoder (built on the host from the coder's tables, ~1.7 KiB; the decode kernels keep a copy in LDS)
 struct DecoderTables {
@@ -680,6 +683,27 @@ ICER_HD void decode_chain(PlaneDecoder &p, uint16_t *plane, size_t stride, const
         while (p.status == 1) plane_step(p, plane + c.first, c.w, c.h, stride, subband, sign_bit, t);
         if (p.status != kOk) break;
     }
+}
+
+// The same for a chain of a decode session: the planes marked kHeldPlane are in `plane` already (nothing else of a plane
+// outlives it: a packet's context model starts fresh), so resuming is starting the loop at the first plane that has a packet.
+// *lowest_ok: the lowest plane that is held or ended kOk (`planes`: none) -- the host learns from it where a chain stopped.
+ICER_HD void decode_chain_resume(PlaneDecoder &p, uint16_t *plane, size_t stride, const ChainDesc &c, int subband, const uint8_t *stream,
+                                 uint32_t stream_len, const DecoderTables &t, int planes, int sign_bit, uint32_t *lowest_ok)
+{
+    int ok = planes;
+    for (int lsb = planes - 1; lsb >= 0; lsb--) {
+        const uint32_t at = c.pkt[lsb];
+        if (at == kNoPacket) break;
+        if (at != kHeldPlane) {
+            entropy_init(p.d, stream, stream_len, at + (uint32_t)kHeaderBytes, packet_bits(stream, at));
+            plane_begin(p, lsb, sign_bit, c.w, c.h);
+            while (p.status == 1) plane_step(p, plane + c.first, c.w, c.h, stride, subband, sign_bit, t);
+            if (p.status != kOk) break;
+        }
+        ok = lsb;
+    }
+    *lowest_ok = (uint32_t)ok;
 }
 
 // ---- the planes of a chain side by side.  Plane lsb reads, of the plane above, the samples to the right and in the

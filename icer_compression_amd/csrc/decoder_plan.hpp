@@ -203,44 +203,23 @@ struct DecodePlan {
     uint32_t chains_full = 0;
 };
 
-// `cands`: the candidates of ONE stream, sorted by offset.  *w / *h: in = the caller's values (kept when the stream holds no valid packet).
-// `reduce` = r > 0 (a reduced-resolution decoder, include/icer_hip_dec.h): `stages` is the decoder's S - r, and the walk reads
-// the stream as its derived stream -- a valid packet of level <= r moves the cursor and nothing else, any other counts as
-// level - r of an image of ceil(w / 2^r) x ceil(h / 2^r).
-// `where` (window decode): of each chain its level and its rectangle inside its subband.
-inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cands, int channels,
-                        int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce = 0,
-                        std::vector<std::pair<int, Rect>> *where = nullptr)
+// [chan][level][subband][segment][lsb] -> packet offset (kNoPacket: none) and that packet's data_length
+struct PacketTable {
+    std::vector<uint32_t> off, bits;
+    PacketTable() : off((size_t)3 * (kMaxStages + 1) * 4 * (kMaxSegments + 1) * kPlanes, kNoPacket), bits(off.size(), 0u) {}
+    static size_t chain_index(int ch, int lv, int sb, int sg) { return (((size_t)ch * (kMaxStages + 1) + lv) * 4 + sb) * (kMaxSegments + 1) + sg; }
+    static size_t index(int ch, int lv, int sb, int sg, int lsb) { return chain_index(ch, lv, sb, sg) * kPlanes + lsb; }
+    // does a header name an entry?  (level `lv`: already less the decoder's reduce)
+    static bool names(int ch, int lv, int sb, int sg, int lsb) { return lv >= 0 && lv <= kMaxStages && sb < 4 && sg <= kMaxSegments && lsb < kPlanes && ch < 3; }
+};
+
+// The second half of plan_decode, from the packet table of a w x h image (pl->w, pl->h, pl->mean set) to its chains, levels
+// and return code.  A decode session (decoder_session.hpp) calls it with a table of its own, whose held planes read kHeldPlane.
+// `keys`: of each chain its PacketTable::chain_index.
+inline void plan_chains(DecodePlan *pl, const PacketTable &tab, int channels, int stages, unsigned segments, int planes, size_t bufsize,
+                        std::vector<std::pair<int, Rect>> *where = nullptr, std::vector<size_t> *keys = nullptr)
 {
-    const int planes = sample_bits == 8 ? kPlanes8 : kPlanes;
-    *pl = DecodePlan();
-    pl->w = w_in; pl->h = h_in;
-    if (channels != 1 && channels != 3) { pl->rc = kInvalidInput; return; }
-    if (stages < 1 || stages > kMaxStages) { pl->rc = kTooManyStages; return; }      // (reference: out-of-bounds table)
-    // [chan][level][subband][segment][lsb] -> packet offset; the last packet of a kind wins
-    std::vector<uint32_t> table((size_t)3 * (kMaxStages + 1) * 4 * (kMaxSegments + 1) * kPlanes, kNoPacket);
-    std::vector<uint32_t> bits_tab(table.size(), 0u);              // ... and that packet's data_length
-    auto slot_index = [&](int ch, int lv, int sb, int sg, int lsb) {
-        return ((((size_t)ch * (kMaxStages + 1) + lv) * 4 + sb) * (kMaxSegments + 1) + sg) * kPlanes + lsb;
-    };
-    auto slot = [&](int ch, int lv, int sb, int sg, int lsb) -> uint32_t & { return table[slot_index(ch, lv, sb, sg, lsb)]; };
-    // the scan accepts a candidate when it starts at or behind the end of the previous packet and both CRCs hold;
-    // anything else is stepped over byte by byte
-    uint32_t cursor = 0;
-    for (const PacketCandidate &c : cands) {
-        if (c.off < cursor || !c.fits || !c.payload_ok) continue;
-        const uint8_t *p = c.hdr;
-        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
-        if ((int)p[4] <= reduce && reduce > 0) continue;          // (dropped from the derived stream)
-        const int lv = p[4] - reduce, sb = p[5], sg = p[6], lsb = p[7] & 15, ch = channels == 3 ? (p[7] >> 4) : 0;
-        if (lv <= kMaxStages && sb < 4 && sg <= kMaxSegments && lsb < kPlanes && ch < 3) {
-            slot(ch, lv, sb, sg, lsb) = c.off;
-            bits_tab[slot_index(ch, lv, sb, sg, lsb)] = load_le32(p + 16);
-        }
-        pl->w = reduced_dim(load_le32(p + 8), reduce);
-        pl->h = reduced_dim(load_le32(p + 12), reduce);
-        if (ch < 3) pl->mean[ch] = (uint16_t)(p[2] | (p[3] << 8));
-    }
+    auto slot = [&](int ch, int lv, int sb, int sg, int lsb) { return tab.off[PacketTable::index(ch, lv, sb, sg, lsb)]; };
     if (bufsize < pl->w * pl->h) { pl->rc = kByteQuotaExceeded; return; }
     const size_t w = pl->w, h = pl->h;
     std::vector<Rect> rects;
@@ -270,9 +249,10 @@ inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cand
                     for (int lsb = 0; lsb < kPlanes; lsb++) c.pkt[lsb] = lsb < planes ? slot(ch, lv, sb, (int)sg, lsb) : kNoPacket;
                     c.fast = (c.w > 0 && c.h > 0) ? 1u : 0u;
                     for (int lsb = planes - 1; lsb >= 0 && c.pkt[lsb] != kNoPacket; lsb--)
-                        if (bits_tab[slot_index(ch, lv, sb, (int)sg, lsb)] < kFastPacketBits) c.fast = 0u;
+                        if (tab.bits[PacketTable::index(ch, lv, sb, (int)sg, lsb)] < kFastPacketBits) c.fast = 0u;
                     pl->chains.push_back(c);
                     if (where) where->push_back({lv, rects[sg]});
+                    if (keys) keys->push_back(PacketTable::chain_index(ch, lv, sb, (int)sg));
                 }
             }
     if (pl->rc != kOk) return;
@@ -280,6 +260,42 @@ inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cand
     if (dim_low(w, stages) >= 3 && dim_low(h, stages) >= 3)
         for (int it = 1; it <= stages; it++)
             pl->levels.push_back(DecodeLevel{(uint32_t)dim_low(w, stages - it), (uint32_t)dim_low(h, stages - it)});
+}
+
+// `cands`: the candidates of ONE stream, sorted by offset.  *w / *h: in = the caller's values (kept when the stream holds no valid packet).
+// `reduce` = r > 0 (a reduced-resolution decoder, include/icer_hip_dec.h): `stages` is the decoder's S - r, and the walk reads
+// the stream as its derived stream -- a valid packet of level <= r moves the cursor and nothing else, any other counts as
+// level - r of an image of ceil(w / 2^r) x ceil(h / 2^r).
+// `where` (window decode): of each chain its level and its rectangle inside its subband.
+inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cands, int channels,
+                        int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce = 0,
+                        std::vector<std::pair<int, Rect>> *where = nullptr)
+{
+    const int planes = sample_bits == 8 ? kPlanes8 : kPlanes;
+    *pl = DecodePlan();
+    pl->w = w_in; pl->h = h_in;
+    if (channels != 1 && channels != 3) { pl->rc = kInvalidInput; return; }
+    if (stages < 1 || stages > kMaxStages) { pl->rc = kTooManyStages; return; }      // (reference: out-of-bounds table)
+    // the last packet of a kind wins
+    PacketTable tab;
+    // the scan accepts a candidate when it starts at or behind the end of the previous packet and both CRCs hold;
+    // anything else is stepped over byte by byte
+    uint32_t cursor = 0;
+    for (const PacketCandidate &c : cands) {
+        if (c.off < cursor || !c.fits || !c.payload_ok) continue;
+        const uint8_t *p = c.hdr;
+        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
+        if ((int)p[4] <= reduce && reduce > 0) continue;          // (dropped from the derived stream)
+        const int lv = p[4] - reduce, sb = p[5], sg = p[6], lsb = p[7] & 15, ch = channels == 3 ? (p[7] >> 4) : 0;
+        if (PacketTable::names(ch, lv, sb, sg, lsb)) {
+            tab.off[PacketTable::index(ch, lv, sb, sg, lsb)] = c.off;
+            tab.bits[PacketTable::index(ch, lv, sb, sg, lsb)] = load_le32(p + 16);
+        }
+        pl->w = reduced_dim(load_le32(p + 8), reduce);
+        pl->h = reduced_dim(load_le32(p + 12), reduce);
+        if (ch < 3) pl->mean[ch] = (uint16_t)(p[2] | (p[3] << 8));
+    }
+    plan_chains(pl, tab, channels, stages, segments, planes, bufsize, where);
 }
 
 // The plan of a window decode (`window`: x, y, w, h in pixels of the delivered image): the plan of the plain call, less the

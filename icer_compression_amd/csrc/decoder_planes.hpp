@@ -128,14 +128,16 @@ struct PlaneWave {
 // count, without a per-lane guard.)
 #define PW_BIN(FZ, TOTAL) ((uint32_t)popc64(BALLOT((((FZ) << 16) >= (TOTAL) * LV(p.tc)))))
 
-ICER_DEV void pw_init(PlaneWave &p, uint32_t j, uint32_t nrun, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane,
-                      size_t stride, const uint8_t *stream, uint32_t stream_len, const DecoderTables *t)
+// wave j of nrun decodes plane `lsb` of the chain (pw_init: the chain's planes from the top, wave j plane planes - 1 - j; a
+// resumed chain of a decode session: the planes below the held ones, pw_run_chain_resume)
+ICER_DEV void pw_init_at(PlaneWave &p, uint32_t j, uint32_t nrun, uint32_t lsb, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane,
+                         size_t stride, const uint8_t *stream, uint32_t stream_len, const DecoderTables *t)
 {
     DECL_LANE;
     // (every scalar of the wave's state is made uniform explicitly -- v_readfirstlane -- so that the decision chain below is
     // compiled for the scalar unit with real branches; a value the compiler cannot prove uniform would drag it all onto EXEC
     // masks)
-    p.j = PW_UNIFORM(j); p.nrun = PW_UNIFORM(nrun); p.lsb = PW_UNIFORM((uint32_t)planes - 1u - j);
+    p.j = PW_UNIFORM(j); p.nrun = PW_UNIFORM(nrun); p.lsb = PW_UNIFORM(lsb);
     p.w = PW_UNIFORM((uint32_t)c.w); p.h = PW_UNIFORM((uint32_t)c.h);
     p.pitch = pw_ring_pitch(p.w); p.rows = PW_UNIFORM(pw_ring_rows(planes));
     p.r = 0; p.c = 0; p.done = 0; p.prev = 0; p.sign_bit = PW_UNIFORM((uint32_t)sign_bit); p.mask = (1u << p.sign_bit) - 1u;
@@ -162,6 +164,21 @@ ICER_DEV void pw_init(PlaneWave &p, uint32_t j, uint32_t nrun, const ChainDesc &
     p.bin_half = PW_BIN(1u, 2u);
     PW_LOAD_CHUNK(p.pay, 0u)
     PW_LOAD_CHUNK(p.pay2, 1u)
+}
+ICER_DEV void pw_init(PlaneWave &p, uint32_t j, uint32_t nrun, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane,
+                      size_t stride, const uint8_t *stream, uint32_t stream_len, const DecoderTables *t)
+{
+    pw_init_at(p, j, nrun, (uint32_t)planes - 1u - j, c, planes, sign_bit, plane, stride, stream, stream_len, t);
+}
+// the loader wave of a resumed chain (pw_load_step) decodes nothing: of the wave's state it has the geometry, the row counter
+// and the progress count alone.  Always wave 0.
+ICER_DEV void pw_init_loader(PlaneWave &p, uint32_t nrun, const ChainDesc &c, int planes, uint16_t *plane, size_t stride)
+{
+    p.j = 0; p.nrun = PW_UNIFORM(nrun); p.lsb = 0;
+    p.w = PW_UNIFORM((uint32_t)c.w); p.h = PW_UNIFORM((uint32_t)c.h);
+    p.pitch = pw_ring_pitch(p.w); p.rows = PW_UNIFORM(pw_ring_rows(planes));
+    p.r = 0; p.c = 0; p.done = 0; p.prev = 0; p.retired = 0;
+    p.seg = plane + PW_UNIFORM(c.first); p.stride = stride;
 }
 
 // a < b as a 0 / 1 word, for values below 2^31: the borrow of a - b.  (Written as a comparison the compiler keeps the truth value
@@ -440,6 +457,56 @@ ICER_DEV int pw_step(PlaneWave &p, PwShared &s, uint16_t *zero_row, uint16_t *ri
     return p.r >= h ? 2 : 1;
 }
 
+// One step of the LOADER wave of a resumed chain (a decode session, decoder_session.hpp): the chain's upper planes are in the
+// state plane (p.seg) from earlier feeds, and wave 0 stands where the top plane stands in a chain decoded in one go -- it
+// copies row p.r of the segment into its ring slot, 64 samples per instruction, and publishes done[0] like a plane.  The
+// planes below run pw_step as it is: they read the held bits from rowC / rowU / rowD.  Paced by the top plane's rule
+// (pw_wait_for with j == 0: the slot of row r + 1 has been recycled; row r's was the step before).  Returns as pw_step.
+ICER_DEV int pw_load_step(PlaneWave &p, PwShared &s, uint16_t *ring)
+{
+    DECL_LANE;
+    if (p.r >= p.h) return 2;
+    {
+        uint32_t need;
+        const uint32_t *word = pw_wait_for(p, s, &need);
+        if (PW_UNIFORM(PW_LDS_LOAD(*word)) < need) return 0;
+    }
+    PW_FENCE_ACQ();
+    uint16_t *slot = ring + (size_t)(p.r % p.rows) * p.pitch + 1u;
+    for (uint32_t x0 = 0; x0 < p.w; x0 += 64u) {
+        FOR_LANES
+        {
+            // (lanes past the row's end repeat its last sample, as in pw_retire)
+            const uint32_t x = x0 + (uint32_t)lane < p.w ? x0 + (uint32_t)lane : p.w - 1u;
+            slot[x] = p.seg[(size_t)p.r * p.stride + x];
+        }
+    }
+    p.done += p.w;
+    p.r++;
+    WAVE_SYNC();
+    PW_FENCE_REL();
+    FOR_LANES { PW_LDS_STORE(s.done[0], p.done); }
+    return p.r >= p.h ? 2 : 1;
+}
+
+// the waves of a chain in a decode session: `held` planes from the top are marked kHeldPlane, `fresh` packets follow them.
+// Nothing held: the chain's waves are those of pw_run_chain.  Else wave 0 loads and wave j >= 1 decodes plane planes - held - j.
+struct PwResume { uint32_t held, fresh, nrun; };
+ICER_DEV PwResume pw_resume_shape(const ChainDesc &c, int planes)
+{
+    PwResume s = {0u, 0u, 0u};
+    while ((int)s.held < planes && PW_UNIFORM(c.pkt[planes - 1 - (int)s.held]) == kHeldPlane) s.held++;
+    while ((int)(s.held + s.fresh) < planes && PW_UNIFORM(c.pkt[planes - 1 - (int)(s.held + s.fresh)]) < kHeldPlane) s.fresh++;
+    s.nrun = s.fresh ? s.fresh + (s.held ? 1u : 0u) : 0u;
+    return s;
+}
+ICER_DEV void pw_init_resume(PlaneWave &p, uint32_t j, const PwResume &s, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane,
+                             size_t stride, const uint8_t *stream, uint32_t stream_len, const DecoderTables *t)
+{
+    if (s.held && j == 0u) pw_init_loader(p, s.nrun, c, planes, plane, stride);
+    else pw_init_at(p, j, s.nrun, (uint32_t)planes - s.held - j - (s.held ? 0u : 1u), c, planes, sign_bit, plane, stride, stream, stream_len, t);
+}
+
 
 // All planes of one chain: the body of decode_chains_planes_kernel.  GPU build: called by every wavefront of the workgroup
 // (wave `wave` of kPwWaves; `lds` = pw_lds_bytes(c.w, planes) bytes, zeroed by the workgroup before); a wave that waits
@@ -468,7 +535,58 @@ ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t /*wave*/, const ChainDesc &c, 
         if (!progress) return false;
     }
 }
+// the same for a chain of a decode session (pw_resume_shape): the loader in wave 0's place when planes are held
+ICER_DEV bool pw_run_chain_resume(uint8_t *lds, uint32_t /*wave*/, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
+                                  const uint8_t *stream, uint32_t stream_len, const DecoderTables *t, uint32_t * /*err*/)
+{
+    memset(lds, 0, pw_lds_bytes(c.w, planes));
+    PwShared &sh = *reinterpret_cast<PwShared *>(lds);
+    uint16_t *zero_row = reinterpret_cast<uint16_t *>(lds + sizeof(PwShared)), *ring = zero_row + pw_ring_pitch(c.w);
+    const PwResume s = pw_resume_shape(c, planes);
+    PlaneWave pw[kPlanes];
+    for (uint32_t j = 0; j < s.nrun; j++) pw_init_resume(pw[j], j, s, c, planes, sign_bit, plane, stride, stream, stream_len, t);
+    for (;;) {
+        bool progress = false, all_done = true;
+        for (uint32_t j = 0; j < s.nrun; j++) {
+            const int st = (s.held && j == 0u) ? pw_load_step(pw[j], sh, ring) : pw_step(pw[j], sh, zero_row, ring);
+            progress = progress || st == 1;
+            all_done = all_done && (st == 2 || pw[j].r >= pw[j].h);
+        }
+        if (all_done) return true;
+        if (!progress) return false;
+    }
+}
 #else
+// One wave's share of a chain: its steps (kLoader: pw_load_step, else pw_step), each behind the wait for what it needs.
+// (the loop must leave by wave-UNIFORM conditions only -- the lane-0 store of the error word comes after it: a per-lane
+// branch inside the loop would make every value the loop carries, i.e. the whole decoder state, divergent for the compiler)
+// A waiting wave must not eat the compute unit's ONE scalar unit: with two long chains on a compute unit that unit is
+// what they share (profiles/r04_logs/r04_l_planes_sq_counters.log: 0.6-0.75 scalar instructions per cycle and compute
+// unit, and the five upper planes of a chain mostly wait).  So the wait is a loop of its own over ONE word of LDS --
+// what the block needs is computed once (pw_wait_for), a poll is a load, a compare and a sleep -- and the sleep grows
+// with the time waited: 128 cycles for the first polls (a neighbour about to publish), then 1 k, then 8 k cycles.  A
+// long sleep costs a waiting wave nothing: it waits because it is the faster one of a pair and has a row of slack.
+template <bool kLoader>
+ICER_DEV bool pw_wave_loop(PlaneWave &p, PwShared &sh, uint16_t *zero_row, uint16_t *ring, uint32_t *err)
+{
+    bool ok = true;
+    while (p.r < p.h) {
+        uint32_t need;
+        const uint32_t *word = pw_wait_for(p, sh, &need);
+        uint32_t spins = 0;
+        while (PW_UNIFORM(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) {
+            if (spins < 6u) __builtin_amdgcn_s_sleep(2);
+            else if (spins < 12u) __builtin_amdgcn_s_sleep(16);
+            else __builtin_amdgcn_s_sleep(127);
+            spins++;
+            if (spins > kPwSpinLimit || ((spins & 63u) == 0u && PW_UNIFORM(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u)) { ok = false; break; }
+        }
+        if (!ok) break;
+        if ((kLoader ? pw_load_step(p, sh, ring) : pw_step(p, sh, zero_row, ring)) == 0) { ok = false; break; }     // (cannot be: the condition just held and only grows)
+    }
+    if (!ok && (threadIdx.x & 63u) == 0u) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return ok;
+}
 ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t wave, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
                            const uint8_t *stream, uint32_t stream_len, const DecoderTables *t, uint32_t *err)
 {
@@ -480,14 +598,8 @@ ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t wave, const ChainDesc &c, int 
     if (wave >= nrun) return true;
     PlaneWave p;
     pw_init(p, wave, nrun, c, planes, sign_bit, plane, stride, stream, stream_len, t);
-    // (the loop must leave by wave-UNIFORM conditions only -- the lane-0 store of the error word comes after it: a per-lane
-    // branch inside the loop would make every value the loop carries, i.e. the whole decoder state, divergent for the compiler)
-    // A waiting wave must not eat the compute unit's ONE scalar unit: with two long chains on a compute unit that unit is
-    // what they share (profiles/r04_logs/r04_l_planes_sq_counters.log: 0.6-0.75 scalar instructions per cycle and compute
-    // unit, and the five upper planes of a chain mostly wait).  So the wait is a loop of its own over ONE word of LDS --
-    // what the block needs is computed once (pw_wait_for), a poll is a load, a compare and a sleep -- and the sleep grows
-    // with the time waited: 128 cycles for the first polls (a neighbour about to publish), then 1 k, then 8 k cycles.  A
-    // long sleep costs a waiting wave nothing: it waits because it is the faster one of a pair and has a row of slack.
+    // (pw_wave_loop<false>, kept in its own words: routed through the template, the register figures of the kernels that call
+    // this function move, and they are pinned -- profiles/decode_session.md)
     bool ok = true;
     while (p.r < p.h) {
         uint32_t need;
@@ -505,6 +617,23 @@ ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t wave, const ChainDesc &c, int 
     }
     if (!ok && (threadIdx.x & 63u) == 0u) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return ok;
+}
+// the same for a chain of a decode session (pw_resume_shape): wave 0 loads when planes are held, and like every wave it
+// waits in pw_wave_loop -- bounded, asleep, raising *err past the spin bound
+ICER_DEV bool pw_run_chain_resume(uint8_t *lds, uint32_t wave, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
+                                  const uint8_t *stream, uint32_t stream_len, const DecoderTables *t, uint32_t *err)
+{
+    PwShared &sh = *reinterpret_cast<PwShared *>(lds);
+    uint16_t *zero_row = reinterpret_cast<uint16_t *>(lds + sizeof(PwShared)), *ring = zero_row + pw_ring_pitch(PW_UNIFORM((uint32_t)c.w));
+    const PwResume s = pw_resume_shape(c, planes);
+    if (wave >= s.nrun) return true;
+    PlaneWave p;
+    if (s.held && wave == 0u) {                                  // (wave-uniform: the wave number and the chain's table)
+        pw_init_loader(p, s.nrun, c, planes, plane, stride);
+        return pw_wave_loop<true>(p, sh, zero_row, ring, err);
+    }
+    pw_init_resume(p, wave, s, c, planes, sign_bit, plane, stride, stream, stream_len, t);
+    return pw_wave_loop<false>(p, sh, zero_row, ring, err);
 }
 #endif
 

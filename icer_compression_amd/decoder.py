@@ -469,6 +469,106 @@ class Decoder:
                  n, data, data.numel(), offsets, stream_stride, lens, out, frame_stride, rcs, ws, hs)
 
 
+class Session:
+    """A progressive decode session of a Decoder (icerx_session_*, include/icer_hip_dec_session.h): n_slots held frames of
+    frame_stride samples per channel whose coefficient state stays on the device; a feed decodes only the bit planes its
+    packets add and delivers the whole refined image of every fed slot.  The calls are synchronous; the decoder must outlive
+    the session.
+
+        ses = Session(dec, n_slots, frame_stride)
+        ses.feed_torch(cut_a, lens_a, out)                 # the held cut
+        rec.combine_torch(blob, COMBINE_DIFFERENCE, lens_a, lens_b, inc, sizes, rcs, counts)
+        ses.feed_torch(inc, sizes.cpu(), out)              # only the planes cut B adds are decoded
+    """
+
+    def __init__(self, dec: "Decoder", n_slots: int, frame_stride: int):
+        self.dec, self.lib, self.n_slots, self.frame_stride = dec, dec.lib, n_slots, frame_stride
+        self.channels, self.bits = dec.channels, dec.bits
+        self.handle = C.c_void_p()
+        fn = _need(self.lib, "icerx_session_create")
+        _check(self.lib, "icerx_session_create", fn(C.byref(self.handle), dec.handle, n_slots, frame_stride))
+
+    def close(self):
+        if self.handle:
+            self.lib.icerx_session_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, slot: int = -1) -> None:
+        """forget what `slot` holds (-1: every slot)"""
+        rc = self.lib.icerx_session_reset(self.handle, slot)
+        if rc != 0:
+            raise ValueError(f"icerx_session_reset({slot}): {rc}")
+
+    def planes_held(self, slot: int, chan: int, level: int, subband: int, segment: int) -> int:
+        """bit planes the chain holds, from the top; -1: stopped for good; -2: no such slot or chain"""
+        return int(self.lib.icerx_session_planes_held(self.handle, slot, chan, level, subband, segment))
+
+    def stats(self):
+        """[chains resumed in the wave-per-plane kernel, chains run in the thread-per-chain kernel, planes decoded, packets
+        dropped] since creation"""
+        out = (C.c_uint64 * 4)()
+        _check(self.lib, "icerx_session_stats", self.lib.icerx_session_stats(self.handle, out))
+        return [int(x) for x in out]
+
+    def _feed(self, fn, n: int, slots, data: int, offsets, lens, out, sizes=None):
+        """one of the three feed calls, its per-frame host arrays packed here; -> (rc, rcs, ws, hs)"""
+        m = max(n, 1)
+        offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
+        sizes = sizes or [(0, 0)] * n
+        rcs, ws, hs = (C.c_int * m)(), (_sz * m)(*[int(s[0]) for s in sizes]), (_sz * m)(*[int(s[1]) for s in sizes])
+        rc = fn(self.handle, n, c_array(C.c_int, slots), data, offs, ln, out, rcs, ws, hs)
+        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+
+    def feed_host(self, feeds, slots=None, sizes=None):
+        """feeds: a list of byte strings in host memory, feed k for slot slots[k] (None: 0 .. n - 1); sizes: (w, h) per feed,
+        used while the slot has seen no valid packet -> (rc, [(rc_k, w_k, h_k, [flat planes of frame_stride samples])])"""
+        n, ch = len(feeds), self.channels
+        lens = [len(f) for f in feeds]
+        offs = [sum(lens[:k]) for k in range(n)]
+        blob = np.frombuffer(b"".join(feeds), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+        planes = [np.zeros(max(self.frame_stride, 1), np.uint16 if self.bits == 16 else np.uint8) for _ in range(n * ch)]
+        ptrs = (C.c_void_p * max(n * ch, 1))(*[a.ctypes.data for a in planes])
+        rc, rcs, ws, hs = self._feed(self.lib.icerx_session_feed_host, n, slots, blob.ctypes.data, offs, lens, ptrs, sizes)
+        return rc, [(rcs[k], ws[k], hs[k], planes[k * ch: (k + 1) * ch]) for k in range(n)]
+
+    def feed_device(self, n: int, d_data: int, offsets, lens, d_out: int, slots=None, sizes=None, display: bool = False):
+        """raw device pointers; d_out as icerx_decode_device (display: as icerx_decode_device_display) for n frames of
+        frame_stride -> (rc, rcs, ws, hs)"""
+        fn = self.lib.icerx_session_feed_device_display if display else self.lib.icerx_session_feed_device
+        return self._feed(fn, n, slots, d_data, offsets, lens, d_out, sizes)
+
+    def feed_torch(self, data, lens, out, offsets=None, stream_stride=None, slots=None, sizes=None, display: bool = False):
+        """Feed n increments of a cuda uint8 tensor and wait.  data: the blob, 1-D, or 2-D (n, stride) with feed k in row k;
+        lens / offsets: host sequences (offsets None: feed k starts at k * stream_stride, default data.stride(0)); out: a
+        contiguous cuda tensor of n * channels * frame_stride samples -- int16 / uint16 (uint8 for an 8-bit decoder), or, with
+        display, uint8 gray8 / RGB888 rows -> (rcs, ws, hs).  A refused call raises."""
+        import torch
+        n = len(lens)
+        want = (torch.uint8,) if display or self.bits == 8 else (torch.int16, getattr(torch, "uint16", torch.int16))
+        _need_tensors(("data", data, torch.uint8), ("out", out, want))
+        if out.numel() != n * self.channels * self.frame_stride:
+            raise ValueError("out must hold n * channels * frame_stride samples")
+        if offsets is None:
+            if stream_stride is None:
+                if data.dim() != 2:
+                    raise ValueError("a 1-D blob needs offsets or stream_stride")
+                stream_stride = data.stride(0)
+            offsets = [k * int(stream_stride) for k in range(n)]
+        if any(int(o) + int(x) > data.numel() for o, x in zip(offsets, lens)):
+            raise ValueError("a feed leaves the blob")
+        with torch.cuda.device(data.device):
+            torch.cuda.current_stream().synchronize()        # (the call runs on the null stream: what made `data` is complete)
+            rc, rcs, ws, hs = self.feed_device(n, data.data_ptr(), offsets, lens, out.data_ptr(), slots, sizes, display)
+        _check(self.lib, "icerx_session_feed_device", rc)
+        return rcs, ws, hs
+
+
 MAX_LADDER = 16                  # ICERX_MAX_LADDER
 COMBINE_UNION, COMBINE_DIFFERENCE = 0, 1         # ICERX_COMBINE_UNION / ICERX_COMBINE_DIFFERENCE
 

@@ -447,6 +447,12 @@ int icerx_wavelet_inverse_device(void *d_planes, int n_planes, size_t w, size_t 
 #include "icer_hip_dec_window.h"
 #undef ICER_HIP_DEC_H_WINDOW_PART
 
+/* Progressive decode sessions -- the coefficient state of held frames kept on the device, a feed decodes only the bit planes its
+ * packets add and delivers the refined image.  Declared and described in icer_hip_dec_session.h. */
+#define ICER_HIP_DEC_H_SESSION_PART 1
+#include "icer_hip_dec_session.h"
+#undef ICER_HIP_DEC_H_SESSION_PART
+
 /* Re-cutting stored masters to a distortion target or a shared byte budget, from the masters and their distortion sidecars:
  * icerx_recutter_create_quality, icerx_recut_device_target_async, icerx_recut_device_budget_async.  Declared and described in
  * icer_hip_dec_quality.h. */
