@@ -378,6 +378,21 @@ size_t resolve_planes_lds(icerx_decoder *d)
 #endif
 }
 
+// Grants `kernel` up to `limit` bytes of dynamic LDS (resolve_planes_lds' figure, for the other kernels that take it) and remembers the
+// answer in *state -- 0: not asked yet, 1: granted, -1: refused, it keeps the 48 KiB a launch gets without asking.  -> the limit that holds
+size_t grant_dynamic_lds(const void *kernel, size_t limit, int *state)
+{
+#ifndef ICER_HOST_MOCK
+    if (limit > 48u * 1024u && *state == 0) {
+        *state = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit) == hipSuccess ? 1 : -1;
+        if (*state < 0) (void)hipGetLastError();
+    }
+    if (*state < 0) limit = std::min(limit, (size_t)48u * 1024u);
+#endif
+    (void)kernel; (void)state;
+    return limit;
+}
+
 // the side streams of a decoder, made by the first call that needs them (none is kept half-made: the next call tries again)
 int ensure_side_streams(icerx_decoder *d)
 {
@@ -405,6 +420,8 @@ int ensure_side_streams(icerx_decoder *d)
 struct BatchOut {
     enum Kind { kHostPlanes, kDevPlanes, kHostDisplay, kDevDisplay } kind;
     const void *p;
+    bool display() const { return kind == kHostDisplay || kind == kDevDisplay; }
+    bool to_host() const { return kind == kHostPlanes || kind == kHostDisplay; }
 };
 
 // one call of decode_batch: what its stages (batch_packets .. batch_results, in this order) hand to one another
@@ -412,8 +429,10 @@ struct BatchRun {
     icerx_decoder *d;
     int n;
     size_t frame_stride;
+    size_t total_len, max_len;           // the end of the last stream in the batch buffer; the longest stream
     PlaneBits pb;
     std::vector<FrameInfo> frames;
+    std::vector<PacketCandidate> cands;  // from batch_packets on: the header candidates, in stream and offset order
     std::vector<DecodePlan> plans;
     std::vector<ChainDesc> chains;       // from batch_chains on: in launch order (route_batch_chains), as uploaded to d->chains
     const uint8_t *d_data;
@@ -426,27 +445,50 @@ struct BatchRun {
     dim3 grid_all() const { return dim3((unsigned)((frame_stride + 255u) / 256u), (unsigned)(n * d->channels)); }
 };
 
+// Opens a call of any synchronous driver, behind the checks that are the driver's own: the streams' bytes and the 32-bit limits of
+// the batch buffer (`too_long`: the driver's sentence, with a %zu) and of the strides (out_stride: 0 but for a window decode)
+int batch_open(BatchRun &run, icerx_decoder *d, int n, const uint8_t *data, const size_t *offsets, const size_t *lens, size_t frame_stride,
+               size_t out_stride, const char *too_long)
+{
+    size_t total_len = 0, max_len = 0;
+    std::vector<FrameInfo> frames((size_t)n);                // (all zero)
+    for (int k = 0; k < n; k++) {
+        if (lens[k] && !data) return ICER_INVALID_INPUT;
+        total_len = std::max(total_len, offsets[k] + lens[k]);
+        max_len = std::max(max_len, lens[k]);
+        frames[k].stream_off = (uint32_t)offsets[k];         // (they fit: the test below)
+        frames[k].stream_len = (uint32_t)lens[k];
+    }
+    if (total_len >= 0xFFFFFFFFull - 64u) return fail(too_long, total_len);
+    if (std::max(frame_stride, out_stride) > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", std::max(frame_stride, out_stride));
+    BatchRun r = {d, n, frame_stride, total_len, max_len, plane_bits(d->bits), std::move(frames), {}, std::vector<DecodePlan>((size_t)n), {},
+                  nullptr, nullptr, nullptr, nullptr, out_stride};
+    run = std::move(r);
+    return ICER_RESULT_OK;
+}
+
 // 1. packets: the streams on the device, their header candidates with checked payloads, in stream and offset order
-int batch_packets(BatchRun &r, const uint8_t *data, bool data_on_device, size_t total_len, size_t max_len, std::vector<PacketCandidate> &cands)
+int batch_packets(BatchRun &r, const uint8_t *data, bool data_on_device)
 {
     icerx_decoder *d = r.d;
+    std::vector<PacketCandidate> &cands = r.cands;
     int rc = ICER_RESULT_OK;
     HIP_TRY(ensure(d->frames, sizeof(FrameInfo) * r.n));
     r.d_frames = (FrameInfo *)d->frames.p;
     HIP_TRY(hipMemcpy(r.d_frames, r.frames.data(), sizeof(FrameInfo) * r.n, hipMemcpyHostToDevice));
-    if (total_len) {
+    if (r.total_len) {
         if (data_on_device) r.d_data = data;
         else {
-            HIP_TRY(ensure(d->data, total_len));
-            HIP_TRY(hipMemcpy(d->data.p, data, total_len, hipMemcpyHostToDevice));
+            HIP_TRY(ensure(d->data, r.total_len));
+            HIP_TRY(hipMemcpy(d->data.p, data, r.total_len, hipMemcpyHostToDevice));
             r.d_data = (const uint8_t *)d->data.p;
         }
         HIP_TRY(ensure(d->count, sizeof(uint32_t)));
-        uint32_t cap = (uint32_t)(total_len / 64u) + 1024u, count = 0;
-        for (int attempt = 0; attempt < 2 && max_len; attempt++) {
+        uint32_t cap = (uint32_t)(r.total_len / 64u) + 1024u, count = 0;
+        for (int attempt = 0; attempt < 2 && r.max_len; attempt++) {
             HIP_TRY(ensure(d->cands, sizeof(PacketCandidate) * cap));
             HIP_TRY(hipMemset(d->count.p, 0, sizeof(uint32_t)));
-            ICER_LAUNCH(count_headers_kernel, dim3((unsigned)((max_len + 255u) / 256u), (unsigned)r.n), 256, 0, r.d_data, r.d_frames,
+            ICER_LAUNCH(count_headers_kernel, dim3((unsigned)((r.max_len + 255u) / 256u), (unsigned)r.n), 256, 0, r.d_data, r.d_frames,
                         (const uint32_t *)d->crc.p, (PacketCandidate *)d->cands.p, cap, (uint32_t *)d->count.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpy(&count, d->count.p, sizeof count, hipMemcpyDeviceToHost));
@@ -468,10 +510,78 @@ done:
     return rc;
 }
 
+// what the kernels are told about a frame with this plan (stream_off / stream_len stay); -> it delivers samples (plan_delivers)
+bool frame_of_plan(FrameInfo &f, const DecodePlan &pl, int stages)
+{
+    const bool runs = plan_delivers(pl);
+    f.w = runs ? (uint32_t)pl.w : 0u;
+    f.h = runs ? (uint32_t)pl.h : 0u;
+    f.ll_w = (uint32_t)dim_low(pl.w, stages); f.ll_h = (uint32_t)dim_low(pl.h, stages);
+    for (int c = 0; c < 3; c++) f.mean[c] = pl.mean[c];
+    f.transform = (runs && pl.transform) ? 1u : 0u;
+    return runs;
+}
+
+// where the working planes of a call live: the caller's buffer when that is device memory of uint16 samples, else d->work
+hipError_t batch_working_planes(BatchRun &r, const BatchOut &out)
+{
+    const bool callers = out.kind == BatchOut::kDevPlanes && r.d->bits == 16;
+    const hipError_t e = callers ? hipSuccess : ensure(r.d->work, sizeof(uint16_t) * r.planes_total());
+    r.d_planes = (uint16_t *)(callers ? const_cast<void *>(out.p) : r.d->work.p);
+    return e;
+}
+
+// the error word of a wave-per-plane launch: cleared in front of it, read once the kernels are complete (`whose`: "the decoder", ...)
+hipError_t planes_err_begin(icerx_decoder *d)
+{
+    const hipError_t e = ensure(d->err, sizeof(uint32_t));
+    return e != hipSuccess ? e : hipMemset(d->err.p, 0, sizeof(uint32_t));
+}
+int planes_err_end(icerx_decoder *d, const char *whose)
+{
+    int rc = ICER_RESULT_OK;
+    uint32_t err = 0;
+    HIP_TRY(hipMemcpy(&err, d->err.p, sizeof err, hipMemcpyDeviceToHost));
+    if (err) rc = fail("a bit-plane wave of %s waited longer than its spin bound (internal error)", whose);
+done:
+    return rc;
+}
+
+// the way out of a call after an error: nothing of it runs on afterwards (launches of the size classes may be left on the side
+// streams), and the error it met is not found again by the next call
+void drain_after_error(icerx_decoder *d)
+{
+#ifndef ICER_HOST_MOCK
+    if (d->side_ok) for (hipStream_t st : d->side) (void)hipStreamSynchronize(st);
+#endif
+    (void)hipDeviceSynchronize(); (void)hipGetLastError();
+}
+
+// the copy back of a host call, from rows of channels * frame_stride units of `unit` bytes at `from`: of frame k its samples(k)
+// samples -- a display call's to the one image pointer of the frame, else each channel's to its plane pointer
+template <class Samples>
+int rows_to_host(const BatchOut &out, int n, int channels, const void *from, size_t frame_stride, size_t unit, Samples samples)
+{
+    void *const *to = (void *const *)out.p;
+    int rc = ICER_RESULT_OK;
+    for (int k = 0; k < n; k++) {
+        const size_t count = samples(k);
+        const uint8_t *row = (const uint8_t *)from + (size_t)k * channels * frame_stride * unit;
+        if (!count) continue;
+        if (out.display()) HIP_TRY(hipMemcpy(to[k], row, channels * count, hipMemcpyDeviceToHost));
+        else
+            for (int c = 0; c < channels; c++)
+                HIP_TRY(hipMemcpy(to[k * channels + c], row + (size_t)c * frame_stride * unit, count * unit, hipMemcpyDeviceToHost));
+    }
+done:
+    return rc;
+}
+
 // 2. plans: per stream the packet walk (plan_decode) -- its results, its FrameInfo (uploaded again) and its chains
-int batch_plans(BatchRun &r, const std::vector<PacketCandidate> &cands, int *rcs, size_t *ws, size_t *hs)
+int batch_plans(BatchRun &r, int *rcs, size_t *ws, size_t *hs)
 {
     const icerx_decoder *d = r.d;
+    const std::vector<PacketCandidate> &cands = r.cands;
     int rc = ICER_RESULT_OK;
     size_t at = 0;
     std::vector<PacketCandidate> mine;
@@ -487,13 +597,7 @@ int batch_plans(BatchRun &r, const std::vector<PacketCandidate> &cands, int *rcs
         } else
             plan_decode(&pl, mine, d->channels, d->stages, d->segments, d->bits, ws[k], hs[k], r.frame_stride, d->reduce);
         ws[k] = pl.w; hs[k] = pl.h; rcs[k] = pl.rc;
-        const bool runs = !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
-        f.w = runs ? (uint32_t)pl.w : 0u;
-        f.h = runs ? (uint32_t)pl.h : 0u;
-        f.ll_w = (uint32_t)dim_low(pl.w, d->stages); f.ll_h = (uint32_t)dim_low(pl.h, d->stages);
-        for (int c = 0; c < 3; c++) f.mean[c] = pl.mean[c];
-        f.transform = (runs && pl.transform) ? 1u : 0u;
-        if (!runs) continue;
+        if (!frame_of_plan(f, pl, d->stages)) continue;
         for (ChainDesc c : pl.chains) { c.frame = (uint32_t)k; r.chains.push_back(c); }
     }
     HIP_TRY(hipMemcpy(r.d_frames, r.frames.data(), sizeof(FrameInfo) * r.n, hipMemcpyHostToDevice));
@@ -508,8 +612,7 @@ int batch_chains(BatchRun &r, const BatchOut &out)
     icerx_decoder *d = r.d;
     const int channels = d->channels, nplanes = r.pb.nplanes, sign_bit = r.pb.sign_bit;
     int rc = ICER_RESULT_OK;
-    if (out.kind == BatchOut::kDevPlanes && d->bits == 16) r.d_planes = (uint16_t *)out.p;
-    else { HIP_TRY(ensure(d->work, sizeof(uint16_t) * r.planes_total())); r.d_planes = (uint16_t *)d->work.p; }
+    HIP_TRY(batch_working_planes(r, out));
     // (only the w * h samples of a frame are defined results; the rest of its slot is scratch)
     HIP_TRY(hipMemset(r.d_planes, 0, sizeof(uint16_t) * r.planes_total()));
     if (!r.chains.empty()) {
@@ -525,8 +628,7 @@ int batch_chains(BatchRun &r, const BatchOut &out)
         HIP_TRY(hipMemcpy(d->chains.p, r.chains.data(), sizeof(ChainDesc) * nc, hipMemcpyHostToDevice));
         const ChainDesc *d_chains = (const ChainDesc *)d->chains.p;
         if (n_fast) {
-            HIP_TRY(ensure(d->err, sizeof(uint32_t)));
-            HIP_TRY(hipMemset(d->err.p, 0, sizeof(uint32_t)));
+            HIP_TRY(planes_err_begin(d));
             ICER_LAUNCH_PLANES(decode_chains_planes_kernel, n_fast, route.planes_lds, r.d_planes, r.frame_stride, channels, d_chains, r.d_data,
                                r.d_frames, tables, nplanes, sign_bit, (uint32_t *)d->err.p);
             HIP_TRY(hipGetLastError());
@@ -554,11 +656,7 @@ int batch_chains(BatchRun &r, const BatchOut &out)
             }
             HIP_TRY(hipGetLastError());
         }
-        if (n_fast) {
-            uint32_t err = 0;
-            HIP_TRY(hipMemcpy(&err, d->err.p, sizeof err, hipMemcpyDeviceToHost));
-            if (err) rc = fail("a bit-plane wave of the decoder waited longer than its spin bound (internal error)");
-        }
+        if (n_fast) rc = planes_err_end(d, "the decoder");
     }
 done:
     return rc;
@@ -629,7 +727,7 @@ int batch_results(BatchRun &r, const BatchOut &out)
 {
     icerx_decoder *d = r.d;
     const int n = r.n, channels = d->channels, bits = d->bits;
-    const bool display = out.kind == BatchOut::kHostDisplay || out.kind == BatchOut::kDevDisplay, to_host = out.kind == BatchOut::kHostPlanes || out.kind == BatchOut::kHostDisplay;
+    const bool display = out.display(), to_host = out.to_host();
     uint8_t *d_bytes = to_host ? nullptr : (uint8_t *)out.p;  // the device's bytes: the display images, or the uint8 samples of 8-bit planes
     int rc = ICER_RESULT_OK;
     if (to_host && (display || bits == 8)) {                 // (a host call: they go through a buffer of the decoder's)
@@ -644,21 +742,9 @@ int batch_results(BatchRun &r, const BatchOut &out)
         ICER_LAUNCH(finish_kernel, r.grid_all(), 256, 0, r.d_planes, r.frame_stride, channels, r.d_frames, bits == 8 ? d_bytes : nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    for (int k = 0; k < n && to_host; k++) {
-        const size_t samples = (size_t)r.frames[k].w * r.frames[k].h;
-        if (!samples) continue;
-        switch (out.kind) {
-        case BatchOut::kHostDisplay:
-            HIP_TRY(hipMemcpy(((uint8_t *const *)out.p)[k], d_bytes + (size_t)k * channels * r.frame_stride, channels * samples, hipMemcpyDeviceToHost));
-            break;
-        default:
-            for (int c = 0; c < channels; c++) {
-                const size_t at = ((size_t)k * channels + c) * r.frame_stride;
-                if (bits == 8) HIP_TRY(hipMemcpy(((void *const *)out.p)[k * channels + c], d_bytes + at, samples, hipMemcpyDeviceToHost));
-                else HIP_TRY(hipMemcpy(((void *const *)out.p)[k * channels + c], r.d_planes + at, sizeof(uint16_t) * samples, hipMemcpyDeviceToHost));
-            }
-        }
-    }
+    if (to_host)                                             // (16-bit planes come from the working planes themselves)
+        rc = rows_to_host(out, n, channels, display || bits == 8 ? (const void *)d_bytes : (const void *)r.d_planes, r.frame_stride,
+                          display ? 1u : (size_t)(bits / 8), [&](int k) { return (size_t)r.frames[k].w * r.frames[k].h; });
 done:
     return rc;
 }
@@ -671,34 +757,34 @@ int decode_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_on_devi
     g_error.clear();
     if (!d || n < 0 || (n && (!offsets || !lens || !rcs || !ws || !hs)) || (!out.p && n)) return ICER_INVALID_INPUT;
     if (n == 0) return ICER_RESULT_OK;
-    size_t total_len = 0, max_len = 0;
-    for (int k = 0; k < n; k++) {
-        if (lens[k] && !data) return ICER_INVALID_INPUT;
-        total_len = std::max(total_len, offsets[k] + lens[k]);
-        max_len = std::max(max_len, lens[k]);
-    }
-    if (total_len >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", total_len);
-    if (frame_stride > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", frame_stride);
-
-    BatchRun r = {d, n, frame_stride, plane_bits(d->bits), std::vector<FrameInfo>((size_t)n), std::vector<DecodePlan>((size_t)n), {}, nullptr, nullptr, nullptr};
-    std::vector<PacketCandidate> cands;
-    for (int k = 0; k < n; k++) {
-        memset(&r.frames[k], 0, sizeof(FrameInfo));
-        r.frames[k].stream_off = (uint32_t)offsets[k];
-        r.frames[k].stream_len = (uint32_t)lens[k];
-    }
-    int rc = batch_packets(r, data, data_on_device, total_len, max_len, cands);
-    if (rc == ICER_RESULT_OK) rc = batch_plans(r, cands, rcs, ws, hs);
+    BatchRun r;
+    int rc = batch_open(r, d, n, data, offsets, lens, frame_stride, 0, "batch of %zu stream bytes: 32-bit offsets only");
+    if (rc != ICER_RESULT_OK) return rc;
+    rc = batch_packets(r, data, data_on_device);
+    if (rc == ICER_RESULT_OK) rc = batch_plans(r, rcs, ws, hs);
     if (rc == ICER_RESULT_OK && r.planes_total()) {
         rc = batch_chains(r, out);
         if (rc == ICER_RESULT_OK) rc = batch_samples(r);
         if (rc == ICER_RESULT_OK) rc = batch_results(r, out);
     }
-#ifndef ICER_HOST_MOCK
-    // (an error exit may leave launches of the size classes behind on the side streams: nothing of this call runs on after it)
-    if (rc != ICER_RESULT_OK && d->side_ok) { for (hipStream_t st : d->side) (void)hipStreamSynchronize(st); (void)hipDeviceSynchronize(); (void)hipGetLastError(); }
-#endif
+    if (rc != ICER_RESULT_OK) drain_after_error(d);
     return rc;
+}
+
+// A one-shot call: a decoder of its own (the caller's current device; reduced, rebuilding at `eighths`) for one frame at offset
+// 0 -- run(d, &off, &frame_rc) is the driver's call -- and gone again; -> the call's code if it failed, else the frame's
+template <class Run>
+int one_shot(int channels, int stages, int filt, unsigned segments, int bits, int reduce, int eighths, Run run)
+{
+    icerx_decoder *d = nullptr;
+    int rc = icerx_decoder_create_reduced(&d, -1, channels, stages, filt, segments, bits, reduce);
+    if (rc != ICER_RESULT_OK) return rc;
+    d->recon = eighths;
+    const size_t off = 0;
+    int frame_rc = ICER_RESULT_OK;
+    rc = run(d, &off, &frame_rc);
+    icerx_decoder_destroy(d);
+    return rc != ICER_RESULT_OK ? rc : frame_rc;
 }
 
 int decompress_planes(void *const planes[], int channels, size_t *image_w, size_t *image_h, size_t bufsize,
@@ -708,15 +794,9 @@ int decompress_planes(void *const planes[], int channels, size_t *image_w, size_
     if (!image_w || !image_h || (!data && data_length) || eighths < 0 || eighths > kReconMax) return ICER_INVALID_INPUT;
     for (int c = 0; c < channels; c++)
         if (!planes[c]) return ICER_INVALID_INPUT;
-    icerx_decoder *d = nullptr;
-    int rc = icerx_decoder_create_reduced(&d, -1, channels, stages, filt, segments, bits, reduce);
-    if (rc != ICER_RESULT_OK) return rc;
-    d->recon = eighths;
-    const size_t off = 0;
-    int frame_rc = ICER_RESULT_OK;
-    rc = decode_batch(d, 1, data, false, &off, &data_length, {BatchOut::kHostPlanes, planes}, bufsize, &frame_rc, image_w, image_h);
-    icerx_decoder_destroy(d);
-    return rc != ICER_RESULT_OK ? rc : frame_rc;
+    return one_shot(channels, stages, filt, segments, bits, reduce, eighths, [&](icerx_decoder *d, const size_t *off, int *frame_rc) {
+        return decode_batch(d, 1, data, false, off, &data_length, {BatchOut::kHostPlanes, planes}, bufsize, frame_rc, image_w, image_h);
+    });
 }
 
 }  // namespace
@@ -870,15 +950,10 @@ int icerx_decompress_display(uint8_t *image, size_t *image_w, size_t *image_h, s
                              uint8_t segments, int channels)
 {
     if (!image || !image_w || !image_h || (!datastream && data_length) || (channels != 1 && channels != 3)) return ICER_INVALID_INPUT;
-    icerx_decoder *d = nullptr;
-    int rc = icerx_decoder_create(&d, -1, channels, stages, (int)filt, segments, 16);
-    if (rc != ICER_RESULT_OK) return rc;
-    const size_t off = 0;
-    int frame_rc = ICER_RESULT_OK;
     uint8_t *const images[1] = {image};
-    rc = decode_batch(d, 1, datastream, false, &off, &data_length, {BatchOut::kHostDisplay, images}, image_bufsize_pixels, &frame_rc, image_w, image_h);
-    icerx_decoder_destroy(d);
-    return rc != ICER_RESULT_OK ? rc : frame_rc;
+    return one_shot(channels, stages, (int)filt, segments, 16, 0, 0, [&](icerx_decoder *d, const size_t *off, int *frame_rc) {
+        return decode_batch(d, 1, datastream, false, off, &data_length, {BatchOut::kHostDisplay, images}, image_bufsize_pixels, frame_rc, image_w, image_h);
+    });
 }
 
 #ifdef ICER_DECODE_ASYNC
@@ -947,22 +1022,16 @@ int icerx_decompress_window(void *const planes[], int channels, size_t *image_w,
         return ICER_INVALID_INPUT;
     for (int c = 0; c < channels; c++)
         if (!planes[c]) return ICER_INVALID_INPUT;
-    icerx_decoder *d = nullptr;
-    int rc = icerx_decoder_create_reduced(&d, -1, channels, stages, filt, segments, sample_bits, reduce);
-    if (rc != ICER_RESULT_OK) return rc;
-    d->recon = eighths;
-    // the working planes: the size of the image the stream's first valid packet announces, at the decoder's resolution
-    size_t fw = 0, fh = 0, full = 0;
-    if (datastream && icer_get_image_dimensions(datastream, data_length, &fw, &fh) == ICER_RESULT_OK) {
-        icerx_reduced_size(fw, fh, reduce, &fw, &fh);
-        full = fw * fh;
-    }
-    const size_t off = 0;
-    int frame_rc = ICER_RESULT_OK;
-    rc = decode_window_batch(d, 1, datastream, false, &off, &data_length, window, {BatchOut::kHostPlanes, planes}, bufsize, full, &frame_rc,
-                             image_w, image_h, info);
-    icerx_decoder_destroy(d);
-    return rc != ICER_RESULT_OK ? rc : frame_rc;
+    return one_shot(channels, stages, filt, segments, sample_bits, reduce, eighths, [&](icerx_decoder *d, const size_t *off, int *frame_rc) {
+        // the working planes: the size of the image the stream's first valid packet announces, at the decoder's resolution
+        size_t fw = 0, fh = 0, full = 0;
+        if (datastream && icer_get_image_dimensions(datastream, data_length, &fw, &fh) == ICER_RESULT_OK) {
+            icerx_reduced_size(fw, fh, reduce, &fw, &fh);
+            full = fw * fh;
+        }
+        return decode_window_batch(d, 1, datastream, false, off, &data_length, window, {BatchOut::kHostPlanes, planes}, bufsize, full, frame_rc,
+                                   image_w, image_h, info);
+    });
 }
 
 #ifdef ICER_DECODE_ASYNC

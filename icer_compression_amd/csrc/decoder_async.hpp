@@ -592,17 +592,8 @@ int decode_async(icerx_decoder *d, int n, const uint8_t *d_data, size_t data_byt
         rule.mode = dec_wave_mode();
         rule.nplanes = (uint32_t)nplanes;
         rule.ring_elems_max = (uint32_t)((65536u - sizeof(DecoderTables) - 256u - kStateBytes) / sizeof(uint16_t));
-        size_t limit = resolve_planes_lds(d);
-#ifndef ICER_HOST_MOCK
         // (the list-driven planes kernel asks for the same grant; refused, it keeps what a launch gets without asking)
-        if (limit > 48u * 1024u && d->async_lds_state == 0) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(planes_list_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit) == hipSuccess)
-                d->async_lds_state = 1;
-            else { (void)hipGetLastError(); d->async_lds_state = -1; }
-        }
-        if (d->async_lds_state < 0) limit = std::min(limit, (size_t)48u * 1024u);
-#endif
-        rule.planes_lds_limit = (uint32_t)limit;
+        rule.planes_lds_limit = (uint32_t)grant_dynamic_lds(reinterpret_cast<const void *>(planes_list_kernel), resolve_planes_lds(d), &d->async_lds_state);
     }
 
     if ((rc = ensure_side_streams(d)) != ICER_RESULT_OK) return rc;

@@ -262,11 +262,45 @@ inline void plan_chains(DecodePlan *pl, const PacketTable &tab, int channels, in
             pl->levels.push_back(DecodeLevel{(uint32_t)dim_low(w, stages - it), (uint32_t)dim_low(h, stages - it)});
 }
 
-// `cands`: the candidates of ONE stream, sorted by offset.  *w / *h: in = the caller's values (kept when the stream holds no valid packet).
-// `reduce` = r > 0 (a reduced-resolution decoder, include/icer_hip_dec.h): `stages` is the decoder's S - r, and the walk reads
-// the stream as its derived stream -- a valid packet of level <= r moves the cursor and nothing else, any other counts as
-// level - r of an image of ceil(w / 2^r) x ceil(h / 2^r).
-// `where` (window decode): of each chain its level and its rectangle inside its subband.
+// does a frame with this plan deliver samples?  (the three codes the reference returns before it decodes anything deliver none)
+inline bool plan_delivers(const DecodePlan &pl)
+{
+    return !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
+}
+
+// a packet the walk accepted, its header split: the level less the decoder's reduce, the image size at 1 / 2^reduce
+struct WalkedPacket {
+    uint32_t off, bits;                         // where the packet starts in its stream; its data_length
+    int ch, lv, sb, sg, lsb;
+    size_t w, h;
+    uint16_t mean;
+    bool named() const { return PacketTable::names(ch, lv, sb, sg, lsb); }
+    void enter(PacketTable &tab) const { tab.off[PacketTable::index(ch, lv, sb, sg, lsb)] = off; tab.bits[PacketTable::index(ch, lv, sb, sg, lsb)] = bits; }
+};
+
+// The decoder's definition of which packets of a stream count, written once (the device's copy: walk_frame, decoder_dplan.hpp).
+// `cands`: the candidates of ONE stream, sorted by offset.  The scan accepts a candidate when it starts at or behind the end of
+// the previous packet and both CRCs hold; anything else is stepped over byte by byte.  `reduce` = r > 0 (a reduced-resolution
+// decoder, include/icer_hip_dec.h): the walk reads the stream as its derived stream -- a valid packet of level <= r moves the
+// cursor and nothing else, any other counts as level - r of an image of ceil(w / 2^r) x ceil(h / 2^r).
+// visit(const WalkedPacket &) sees every other accepted packet, in stream order, whether or not its fields name a table entry.
+template <class Visit>
+inline void walk_packets(const std::vector<PacketCandidate> &cands, int channels, int reduce, Visit visit)
+{
+    uint32_t cursor = 0;
+    for (const PacketCandidate &c : cands) {
+        if (c.off < cursor || !c.fits || !c.payload_ok) continue;
+        const uint8_t *p = c.hdr;
+        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
+        if ((int)p[4] <= reduce && reduce > 0) continue;          // (dropped from the derived stream)
+        visit(WalkedPacket{c.off, load_le32(p + 16), channels == 3 ? (p[7] >> 4) : 0, p[4] - reduce, p[5], p[6], p[7] & 15,
+                           (size_t)reduced_dim(load_le32(p + 8), reduce), (size_t)reduced_dim(load_le32(p + 12), reduce),
+                           (uint16_t)(p[2] | (p[3] << 8))});
+    }
+}
+
+// The plan of one stream (walk_packets).  w_in / h_in: the caller's values, kept when the stream holds no valid packet; `stages`: of a
+// reduced-resolution decoder, its S - r; `where` (window decode): of each chain its level and its rectangle inside its subband.
 inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cands, int channels,
                         int stages, unsigned segments, int sample_bits, size_t w_in, size_t h_in, size_t bufsize, int reduce = 0,
                         std::vector<std::pair<int, Rect>> *where = nullptr)
@@ -276,25 +310,13 @@ inline void plan_decode(DecodePlan *pl, const std::vector<PacketCandidate> &cand
     pl->w = w_in; pl->h = h_in;
     if (channels != 1 && channels != 3) { pl->rc = kInvalidInput; return; }
     if (stages < 1 || stages > kMaxStages) { pl->rc = kTooManyStages; return; }      // (reference: out-of-bounds table)
-    // the last packet of a kind wins
+    // the last packet of a kind wins; size and mean are those of the last packet walked, named or not
     PacketTable tab;
-    // the scan accepts a candidate when it starts at or behind the end of the previous packet and both CRCs hold;
-    // anything else is stepped over byte by byte
-    uint32_t cursor = 0;
-    for (const PacketCandidate &c : cands) {
-        if (c.off < cursor || !c.fits || !c.payload_ok) continue;
-        const uint8_t *p = c.hdr;
-        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
-        if ((int)p[4] <= reduce && reduce > 0) continue;          // (dropped from the derived stream)
-        const int lv = p[4] - reduce, sb = p[5], sg = p[6], lsb = p[7] & 15, ch = channels == 3 ? (p[7] >> 4) : 0;
-        if (PacketTable::names(ch, lv, sb, sg, lsb)) {
-            tab.off[PacketTable::index(ch, lv, sb, sg, lsb)] = c.off;
-            tab.bits[PacketTable::index(ch, lv, sb, sg, lsb)] = load_le32(p + 16);
-        }
-        pl->w = reduced_dim(load_le32(p + 8), reduce);
-        pl->h = reduced_dim(load_le32(p + 12), reduce);
-        if (ch < 3) pl->mean[ch] = (uint16_t)(p[2] | (p[3] << 8));
-    }
+    walk_packets(cands, channels, reduce, [&](const WalkedPacket &k) {
+        if (k.named()) k.enter(tab);
+        pl->w = k.w; pl->h = k.h;
+        if (k.ch < 3) pl->mean[k.ch] = k.mean;
+    });
     plan_chains(pl, tab, channels, stages, segments, planes, bufsize, where);
 }
 
@@ -307,7 +329,7 @@ inline void plan_decode_window(DecodePlan *pl, const std::vector<PacketCandidate
 {
     std::vector<std::pair<int, Rect>> where;
     plan_decode(pl, cands, channels, stages, segments, sample_bits, w_in, h_in, bufsize, reduce, &where);
-    const bool runs = !(pl->rc == kInvalidInput || pl->rc == kTooManyStages || pl->rc == kByteQuotaExceeded) && pl->w * pl->h > 0;
+    const bool runs = plan_delivers(*pl);
     win_geom(&pl->win, pl->w, pl->h, stages, runs, pl->transform && !pl->levels.empty(), window, out_stride, pairwise, sample_bits);
     pl->chains_full = runs ? (uint32_t)pl->chains.size() : 0u;
     std::vector<ChainDesc> kept;

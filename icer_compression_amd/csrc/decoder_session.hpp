@@ -115,20 +115,6 @@ int session_reset_slot(icerx_session *s, int slot)
     return ICER_RESULT_OK;
 }
 
-// the dynamic LDS the resume planes kernel may take: the decoder's figure, granted to this kernel too
-size_t session_planes_lds(icerx_session *s)
-{
-    size_t limit = resolve_planes_lds(s->d);
-#ifndef ICER_HOST_MOCK
-    if (limit > 48u * 1024u && s->lds_state == 0) {
-        s->lds_state = hipFuncSetAttribute(reinterpret_cast<const void *>(decode_chains_planes_resume_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit) == hipSuccess ? 1 : -1;
-        if (s->lds_state < 0) (void)hipGetLastError();
-    }
-    if (limit > 48u * 1024u && s->lds_state < 0) limit = 48u * 1024u;
-#endif
-    return limit;
-}
-
 // a chain of a feed that has new planes: hi .. lo
 struct SessionRun { ChainDesc c; int slot; size_t key, recon_at; int hi, lo; };
 
@@ -139,31 +125,24 @@ bool session_accept(icerx_session *s, int k, int slot, const std::vector<PacketC
                     size_t *hs, std::vector<SessionRun> &runs, std::vector<ChainDesc> &recon)
 {
     const icerx_decoder *d = s->d;
-    const int P = plane_bits(d->bits).nplanes, reduce = d->reduce;
+    const int P = plane_bits(d->bits).nplanes;
     icerx_session::Slot &sl = s->slots[(size_t)slot];
     PacketTable feed;
     bool sized = sl.sized, refused = false, has_mean[3] = {sl.has_mean[0], sl.has_mean[1], sl.has_mean[2]};
     size_t w = sl.w, h = sl.h;
     uint16_t mean[3] = {sl.mean[0], sl.mean[1], sl.mean[2]};
     uint64_t walked = 0, accepted = 0;
-    uint32_t cursor = 0;
-    for (const PacketCandidate &c : mine) {                      // (the walk of plan_decode)
-        if (c.off < cursor || !c.fits || !c.payload_ok) continue;
-        const uint8_t *p = c.hdr;
-        cursor = c.off + (uint32_t)kHeaderBytes + c.payload_bytes;
-        if ((int)p[4] <= reduce && reduce > 0) continue;
+    // every walked packet counts; one that names no table entry teaches the slot nothing, one that disagrees with the slot's
+    // size or its channel's mean refuses the feed
+    walk_packets(mine, d->channels, d->reduce, [&](const WalkedPacket &k) {
         walked++;
-        const int lv = p[4] - reduce, sb = p[5], sg = p[6], lsb = p[7] & 15, ch = d->channels == 3 ? (p[7] >> 4) : 0;
-        if (!PacketTable::names(ch, lv, sb, sg, lsb)) continue;
-        const size_t pw = reduced_dim(load_le32(p + 8), reduce), ph = reduced_dim(load_le32(p + 12), reduce);
-        const uint16_t m = (uint16_t)(p[2] | (p[3] << 8));
-        if (!sized) { w = pw; h = ph; sized = true; }
-        else if (pw != w || ph != h) refused = true;
-        if (!has_mean[ch]) { mean[ch] = m; has_mean[ch] = true; }
-        else if (mean[ch] != m) refused = true;
-        feed.off[PacketTable::index(ch, lv, sb, sg, lsb)] = c.off;
-        feed.bits[PacketTable::index(ch, lv, sb, sg, lsb)] = load_le32(p + 16);
-    }
+        if (!k.named()) return;
+        if (!sized) { w = k.w; h = k.h; sized = true; }
+        else if (k.w != w || k.h != h) refused = true;
+        if (!has_mean[k.ch]) { mean[k.ch] = k.mean; has_mean[k.ch] = true; }
+        else if (mean[k.ch] != k.mean) refused = true;
+        k.enter(feed);
+    });
     if (refused) {
         rcs[k] = ICER_INVALID_INPUT;
         if (sl.sized) { ws[k] = sl.w; hs[k] = sl.h; }
@@ -214,35 +193,30 @@ bool session_accept(icerx_session *s, int k, int slot, const std::vector<PacketC
     return true;
 }
 
-int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const uint8_t *data, bool data_on_device, size_t total_len,
-                     size_t max_len, BatchOut out, int *rcs, size_t *ws, size_t *hs, bool *touched)
+int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const uint8_t *data, bool data_on_device, BatchOut out, int *rcs,
+                     size_t *ws, size_t *hs, bool *touched)
 {
     icerx_decoder *d = s->d;
     const int n = r.n, channels = d->channels, nplanes = r.pb.nplanes, sign_bit = r.pb.sign_bit;
-    std::vector<PacketCandidate> cands, mine;
+    std::vector<PacketCandidate> mine;
     std::vector<SessionRun> runs;
     std::vector<ChainDesc> recon, upload;
     std::vector<FrameInfo> by_slot((size_t)s->n_slots);
     std::vector<uint32_t> slot_of_row((size_t)n), lowest;
     uint32_t n_fast = 0, nc = 0;
     size_t planes_lds = 0, at = 0;
-    int rc = batch_packets(r, data, data_on_device, total_len, max_len, cands);
+    int rc = batch_packets(r, data, data_on_device);
     if (rc != ICER_RESULT_OK) return rc;
     *touched = true;
     memset(by_slot.data(), 0, sizeof(FrameInfo) * by_slot.size());
     for (int k = 0; k < n; k++) {
         mine.clear();
-        while (at < cands.size() && cands[at].frame == (uint32_t)k) mine.push_back(cands[at++]);
+        while (at < r.cands.size() && r.cands[at].frame == (uint32_t)k) mine.push_back(r.cands[at++]);
         FrameInfo &f = r.frames[k];
         slot_of_row[(size_t)k] = (uint32_t)slot_of[k];
         DecodePlan &pl = r.plans[k];
         if (!session_accept(s, k, slot_of[k], mine, pl, rcs, ws, hs, runs, recon)) { pl = DecodePlan(); continue; }      // (f.w = f.h = 0: nothing is delivered)
-        const bool delivers = !(pl.rc == kInvalidInput || pl.rc == kTooManyStages || pl.rc == kByteQuotaExceeded) && pl.w * pl.h > 0;
-        f.w = delivers ? (uint32_t)pl.w : 0u;
-        f.h = delivers ? (uint32_t)pl.h : 0u;
-        f.ll_w = (uint32_t)dim_low(pl.w, d->stages); f.ll_h = (uint32_t)dim_low(pl.h, d->stages);
-        for (int c = 0; c < 3; c++) f.mean[c] = pl.mean[c];
-        f.transform = (delivers && pl.transform) ? 1u : 0u;
+        (void)frame_of_plan(f, pl, d->stages);
         by_slot[(size_t)slot_of[k]] = f;
     }
     HIP_TRY(hipMemcpy(r.d_frames, r.frames.data(), sizeof(FrameInfo) * n, hipMemcpyHostToDevice));
@@ -254,7 +228,9 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
     if (!runs.empty()) {
         const int mode = dec_wave_mode();
         const bool want_planes = mode != 0 && mode != 1 && d->tables.lut_ok != 0u;
-        const DRouteRule rule = {mode, (uint32_t)std::min<size_t>(session_planes_lds(s), 0xFFFFFFFFu), 0u, (uint32_t)nplanes};
+        // (the dynamic LDS the resume planes kernel may take: the decoder's figure, granted to this kernel too)
+        const size_t lds_limit = grant_dynamic_lds(reinterpret_cast<const void *>(decode_chains_planes_resume_kernel), resolve_planes_lds(d), &s->lds_state);
+        const DRouteRule rule = {mode, (uint32_t)std::min<size_t>(lds_limit, 0xFFFFFFFFu), 0u, (uint32_t)nplanes};
         // the routing rule of the plain decode (takes_planes), whatever the load; longest chains first within either share
         const auto rest = std::stable_partition(runs.begin(), runs.end(), [&](const SessionRun &x) {
             return takes_planes(rule, x.c, by_slot[(size_t)x.slot].stream_len, want_planes); });
@@ -271,8 +247,7 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
         HIP_TRY(hipMemcpy(s->chains.p, upload.data(), sizeof(ChainDesc) * nc, hipMemcpyHostToDevice));
         const ChainDesc *d_chains = (const ChainDesc *)s->chains.p;
         if (n_fast) {
-            HIP_TRY(ensure(d->err, sizeof(uint32_t)));
-            HIP_TRY(hipMemset(d->err.p, 0, sizeof(uint32_t)));
+            HIP_TRY(planes_err_begin(d));
             ICER_LAUNCH_PLANES(decode_chains_planes_resume_kernel, n_fast, planes_lds, (uint16_t *)s->state.p, s->frame_stride, channels, d_chains,
                                r.d_data, (const FrameInfo *)s->frames.p, tables, nplanes, sign_bit, (uint32_t *)d->err.p);
             HIP_TRY(hipGetLastError());
@@ -287,11 +262,7 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
             lowest.resize(nc - n_fast);
             HIP_TRY(hipMemcpy(lowest.data(), s->status.p, sizeof(uint32_t) * (nc - n_fast), hipMemcpyDeviceToHost));
         }
-        if (n_fast) {
-            uint32_t err = 0;
-            HIP_TRY(hipMemcpy(&err, d->err.p, sizeof err, hipMemcpyDeviceToHost));
-            if (err) { rc = fail("a bit-plane wave of a decode session waited longer than its spin bound (internal error)"); goto done; }
-        }
+        if (n_fast && (rc = planes_err_end(d, "a decode session")) != ICER_RESULT_OK) goto done;
         for (uint32_t i = 0; i < nc; i++) {
             const SessionRun &x = runs[i];
             int last = x.lo;                                    // the lowest plane that was started
@@ -312,8 +283,7 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
         }
     }
     // ---- the fed slots' planes into the working buffer, and from there as the plain decode
-    if (out.kind == BatchOut::kDevPlanes && d->bits == 16) r.d_planes = (uint16_t *)out.p;
-    else { HIP_TRY(ensure(d->work, sizeof(uint16_t) * r.planes_total())); r.d_planes = (uint16_t *)d->work.p; }
+    HIP_TRY(batch_working_planes(r, out));
     ICER_LAUNCH(session_copy_kernel, r.grid_all(), 256, 0, (const uint16_t *)s->state.p, r.d_planes, s->frame_stride, channels, r.d_frames,
                 (const uint32_t *)s->rows.p);
     HIP_TRY(hipGetLastError());
@@ -336,28 +306,19 @@ int session_feed(icerx_session *s, int n, const int *slots, const uint8_t *data,
     if (n == 0) return ICER_RESULT_OK;
     std::vector<int> slot_of((size_t)n);
     std::vector<char> seen((size_t)s->n_slots, 0);
-    size_t total_len = 0, max_len = 0;
     for (int k = 0; k < n; k++) {
         const int slot = slots ? slots[k] : k;
         if (slot < 0 || slot >= s->n_slots || seen[(size_t)slot]) return ICER_INVALID_INPUT;
         seen[(size_t)slot] = 1;
         slot_of[(size_t)k] = slot;
-        if (lens[k] && !data) return ICER_INVALID_INPUT;
-        total_len = std::max(total_len, offsets[k] + lens[k]);
-        max_len = std::max(max_len, lens[k]);
     }
-    if (total_len >= 0xFFFFFFFFull - 64u) return fail("feeds of %zu bytes: 32-bit offsets only", total_len);
-    icerx_decoder *d = s->d;
-    BatchRun r = {d, n, s->frame_stride, plane_bits(d->bits), std::vector<FrameInfo>((size_t)n), std::vector<DecodePlan>((size_t)n), {}, nullptr, nullptr, nullptr};
-    for (int k = 0; k < n; k++) {
-        memset(&r.frames[k], 0, sizeof(FrameInfo));
-        r.frames[k].stream_off = (uint32_t)offsets[k];
-        r.frames[k].stream_len = (uint32_t)lens[k];
-    }
+    BatchRun r;
     bool touched = false;
-    const int rc = session_feed_run(s, r, slot_of.data(), data, data_on_device, total_len, max_len, out, rcs, ws, hs, &touched);
+    int rc = batch_open(r, s->d, n, data, offsets, lens, s->frame_stride, 0, "feeds of %zu bytes: 32-bit offsets only");
+    if (rc != ICER_RESULT_OK) return rc;
+    rc = session_feed_run(s, r, slot_of.data(), data, data_on_device, out, rcs, ws, hs, &touched);
     if (rc != ICER_RESULT_OK && touched) {                       // (the slots may hold half a feed: they start over)
-        (void)hipDeviceSynchronize(); (void)hipGetLastError();
+        drain_after_error(s->d);
         for (int slot : slot_of) (void)session_reset_slot(s, slot);
     }
     return rc;

@@ -287,32 +287,18 @@ int decode_window_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_
     if (!d || n < 0 || (n && (!offsets || !lens || !rcs || !ws || !hs || !windows || !info || !out.p))) return ICER_INVALID_INPUT;
     if (n == 0) return ICER_RESULT_OK;
     const int channels = d->channels, bits = d->bits;
-    const bool display = out.kind == BatchOut::kHostDisplay || out.kind == BatchOut::kDevDisplay;
-    const bool to_host = out.kind == BatchOut::kHostPlanes || out.kind == BatchOut::kHostDisplay;
+    const bool display = out.display(), to_host = out.to_host();
     if (to_host)
         for (int k = 0; k < n * (display ? 1 : channels); k++)
             if (!((void *const *)out.p)[k]) return ICER_INVALID_INPUT;
-    size_t total_len = 0, max_len = 0;
-    for (int k = 0; k < n; k++) {
-        if (lens[k] && !data) return ICER_INVALID_INPUT;
-        total_len = std::max(total_len, offsets[k] + lens[k]);
-        max_len = std::max(max_len, lens[k]);
-    }
-    if (total_len >= 0xFFFFFFFFull - 64u) return fail("batch of %zu stream bytes: 32-bit offsets only", total_len);
-    if (full_stride > 0xFFFFFFFFull || frame_stride > 0xFFFFFFFFull) return fail("frames of %zu samples: 32-bit indices only", std::max(full_stride, frame_stride));
-
-    BatchRun r = {d, n, full_stride, plane_bits(bits), std::vector<FrameInfo>((size_t)n), std::vector<DecodePlan>((size_t)n), {}, nullptr, nullptr, nullptr};
-    r.windows = windows; r.out_stride = frame_stride;
-    std::vector<PacketCandidate> cands;
-    for (int k = 0; k < n; k++) {
-        memset(&r.frames[k], 0, sizeof(FrameInfo));
-        r.frames[k].stream_off = (uint32_t)offsets[k];
-        r.frames[k].stream_len = (uint32_t)lens[k];
-    }
+    BatchRun r;
     const size_t unit = display ? 1u : (size_t)(bits / 8), out_total = (size_t)n * channels * frame_stride * unit;
     void *d_win_out = to_host ? nullptr : const_cast<void *>(out.p);
-    int rc = batch_packets(r, data, data_on_device, total_len, max_len, cands);
-    if (rc == ICER_RESULT_OK) rc = batch_plans(r, cands, rcs, ws, hs);
+    int rc = batch_open(r, d, n, data, offsets, lens, full_stride, frame_stride, "batch of %zu stream bytes: 32-bit offsets only");
+    if (rc != ICER_RESULT_OK) return rc;
+    r.windows = windows;
+    rc = batch_packets(r, data, data_on_device);
+    if (rc == ICER_RESULT_OK) rc = batch_plans(r, rcs, ws, hs);
     for (int k = 0; k < n && rc == ICER_RESULT_OK; k++) {
         const WinGeom &g = r.plans[k].win;
         uint32_t *o = info + (size_t)k * kWinInfo;
@@ -341,22 +327,12 @@ int decode_window_batch(icerx_decoder *d, int n, const uint8_t *data, bool data_
                                         frame_stride, display, span, (hipStream_t)0);
             if (rc != ICER_RESULT_OK) goto done;
             HIP_TRY(hipDeviceSynchronize());
-            for (int k = 0; k < n && to_host; k++) {
-                const WinGeom &g = geoms[k];
-                const size_t samples = g.skip ? 0u : (size_t)g.ww * g.wh;
-                if (!samples) continue;
-                const uint8_t *from = (const uint8_t *)d_win_out + (size_t)k * channels * frame_stride * unit;
-                if (display) HIP_TRY(hipMemcpy(((void *const *)out.p)[k], from, channels * samples, hipMemcpyDeviceToHost));
-                else
-                    for (int c = 0; c < channels; c++)
-                        HIP_TRY(hipMemcpy(((void *const *)out.p)[k * channels + c], from + (size_t)c * frame_stride * unit, samples * unit, hipMemcpyDeviceToHost));
-            }
+            if (to_host)
+                rc = rows_to_host(out, n, channels, d_win_out, frame_stride, unit, [&](int k) { return geoms[k].skip ? (size_t)0 : (size_t)geoms[k].ww * geoms[k].wh; });
         }
     }
 done:
-#ifndef ICER_HOST_MOCK
-    if (rc != ICER_RESULT_OK && d->side_ok) { for (hipStream_t st : d->side) (void)hipStreamSynchronize(st); (void)hipDeviceSynchronize(); (void)hipGetLastError(); }
-#endif
+    if (rc != ICER_RESULT_OK) drain_after_error(d);
     return rc;
 }
 

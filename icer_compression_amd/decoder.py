@@ -100,6 +100,26 @@ def _bytes_through(streams, rows, stride, call):
     return [(int(rcs[k]), out[k, : int(sizes[k])].tobytes()) for k in range(rows)]
 
 
+def _pack(streams):
+    """byte strings -> (blob, offsets, lens): the streams back to back in one host array, and where each lies, as size_t arrays"""
+    lens = [len(s) for s in streams]
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if streams else np.zeros(0, np.uint64)
+    blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+    n = len(streams)
+    return blob, (_sz * n)(*[int(o) for o in offs]), (_sz * n)(*lens)
+
+
+def _per_frame(n: int, offsets, lens, call, sizes=None):
+    """the per-frame host arrays of a synchronous call, at least one entry each, packed once for every driver: call(offsets, lens,
+    rcs, ws, hs) -> (its rc, rcs, ws, hs as lists of n); sizes: (w, h) per frame, what ws / hs hold going in (default 0)"""
+    m = max(n, 1)
+    offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
+    sizes = sizes or [(0, 0)] * n
+    rcs, ws, hs = (C.c_int * m)(), (_sz * m)(*[int(s[0]) for s in sizes]), (_sz * m)(*[int(s[1]) for s in sizes])
+    rc = call(offs, ln, rcs, ws, hs)
+    return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+
+
 def load_library() -> C.CDLL:
     """libicer_hip_dec.so of this package"""
     global _lib
@@ -136,43 +156,29 @@ def decompress(stream: bytes, channels: int, stages: int, filt: int, segments: i
     lib = lib or load_library()
     if channels not in (1, 3):
         raise ValueError("channels must be 1 or 3")
-    if window is not None:
-        fn = _need(lib, "icerx_decompress_window")
-        if bufsize is None:                                  # (the window clipped to the image the stream announces)
-            rc0, w0, h0 = icer_get_image_dimensions(stream, lib)
-            w0, h0 = reduced_size(w0, h0, reduce) if rc0 == 0 else (0, 0)
+    if bufsize is None:                                      # (the image the stream announces, or the window clipped to it)
+        rc0, w0, h0 = icer_get_image_dimensions(stream, lib)
+        w0, h0 = (reduced_size(w0, h0, reduce) if reduce > 0 else (w0, h0)) if rc0 == 0 else (0, 0)
+        bufsize = w0 * h0
+        if window is not None:
             x0, y0 = min(int(window[0]), w0), min(int(window[1]), h0)
             bufsize = min(int(window[2]), w0 - x0) * min(int(window[3]), h0 - y0)
-        buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
-        planes = [np.zeros(max(bufsize, 1), np.uint16 if bits == 16 else np.uint8) for _ in range(channels)]
-        ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
-        win, info = np.asarray(window, np.uint32).copy(), np.zeros(WINDOW_INFO, np.uint32)
-        w, h = _sz(0), _sz(0)
-        rc = fn(ptrs, channels, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, bits, reduce, reconstruct,
-                win.ctypes.data, info.ctypes.data)
-        return rc, w.value, h.value, planes, [int(x) for x in info]
-    if bufsize is None:
-        rc, w, h = icer_get_image_dimensions(stream, lib)
-        if reduce > 0:
-            w, h = reduced_size(w, h, reduce)
-        bufsize = w * h if rc == 0 else 0
     buf = np.frombuffer(stream, dtype=np.uint8).copy() if len(stream) else np.zeros(1, np.uint8)
     planes = [np.zeros(max(bufsize, 1), np.uint16 if bits == 16 else np.uint8) for _ in range(channels)]
-    if reconstruct != 0:
-        fn = _need(lib, "icerx_decompress_reconstructed")
-        ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
-        w, h = _sz(0), _sz(0)
-        rc = fn(ptrs, channels, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, bits, reduce, reconstruct)
-        return rc, w.value, h.value, planes
-    if reduce != 0:
-        fn = _need(lib, "icerx_decompress_reduced")
-        ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
-        w, h = _sz(0), _sz(0)
-        rc = fn(ptrs, channels, C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments, bits, reduce)
-        return rc, w.value, h.value, planes
-    fn = getattr(lib, "icer_decompress_image_" + ("yuv_" if channels == 3 else "") + ("uint16" if bits == 16 else "uint8"))
+    ptrs = (C.c_void_p * channels)(*[p.ctypes.data for p in planes])
     w, h = _sz(0), _sz(0)
-    rc = fn(*[p.ctypes.data for p in planes], C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments)
+    image = (C.byref(w), C.byref(h), bufsize, buf, len(stream), stages, filt, segments)
+    if window is not None:
+        win, info = np.asarray(window, np.uint32).copy(), np.zeros(WINDOW_INFO, np.uint32)
+        rc = _need(lib, "icerx_decompress_window")(ptrs, channels, *image, bits, reduce, reconstruct, win.ctypes.data, info.ctypes.data)
+        return rc, w.value, h.value, planes, [int(x) for x in info]
+    if reconstruct != 0:
+        rc = _need(lib, "icerx_decompress_reconstructed")(ptrs, channels, *image, bits, reduce, reconstruct)
+    elif reduce != 0:
+        rc = _need(lib, "icerx_decompress_reduced")(ptrs, channels, *image, bits, reduce)
+    else:
+        fn = getattr(lib, "icer_decompress_image_" + ("yuv_" if channels == 3 else "") + ("uint16" if bits == 16 else "uint8"))
+        rc = fn(*[p.ctypes.data for p in planes], *image)
     return rc, w.value, h.value, planes
 
 
@@ -279,20 +285,11 @@ class Decoder:
         except Exception:
             pass
 
-    def _pack(self, streams):
-        lens = [len(s) for s in streams]
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if streams else np.zeros(0, np.uint64)
-        blob = np.frombuffer(b"".join(streams), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
-        n = len(streams)
-        return blob, (_sz * n)(*[int(o) for o in offs]), (_sz * n)(*lens)
+    _pack = staticmethod(_pack)
 
     def _sync(self, fn, n: int, data: int, offsets, lens, out, frame_stride: int):
-        """one of the four synchronous calls, its per-frame host arrays packed here; -> (rc, rcs, ws, hs)"""
-        m = max(n, 1)
-        offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
-        rcs, ws, hs = (C.c_int * m)(), (_sz * m)(), (_sz * m)()
-        rc = fn(self.handle, n, data, offs, ln, out, frame_stride, rcs, ws, hs)
-        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+        """one of the four synchronous calls -> (rc, rcs, ws, hs)"""
+        return _per_frame(n, offsets, lens, lambda offs, ln, rcs, ws, hs: fn(self.handle, n, data, offs, ln, out, frame_stride, rcs, ws, hs))
 
     def _sync_host(self, fn, streams, frame_stride: int, arrays):
         """the same for streams in host memory, written to the host arrays `arrays` (in frame order)"""
@@ -369,14 +366,12 @@ class Decoder:
     # ---- window decode: a rectangle of each image, without the chains it does not depend on (include/icer_hip_dec_window.h) ----
     def _sync_window(self, fn, n: int, data: int, offsets, lens, windows, out, frame_stride: int, full_stride: int):
         """one of the three synchronous window calls; windows: n x 4 (x, y, w, h) -> (rc, rcs, ws, hs, info as n lists of 6)"""
-        m = max(n, 1)
-        offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
-        rcs, ws, hs = (C.c_int * m)(), (_sz * m)(), (_sz * m)()
-        win = np.zeros((m, 4), np.uint32)
+        win = np.zeros((max(n, 1), 4), np.uint32)
         win[:n] = np.asarray(windows, np.uint32).reshape(n, 4)
-        info = np.zeros((m, WINDOW_INFO), np.uint32)
-        rc = fn(self.handle, n, data, offs, ln, win.ctypes.data, out, frame_stride, full_stride, rcs, ws, hs, info.ctypes.data)
-        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n], [[int(x) for x in row] for row in info[:n]]
+        info = np.zeros((max(n, 1), WINDOW_INFO), np.uint32)
+        res = _per_frame(n, offsets, lens, lambda offs, ln, rcs, ws, hs: fn(self.handle, n, data, offs, ln, win.ctypes.data, out, frame_stride,
+                                                                           full_stride, rcs, ws, hs, info.ctypes.data))
+        return (*res, [[int(x) for x in row] for row in info[:n]])
 
     def decode_window_host(self, streams, windows, frame_stride: int, full_stride: int):
         """icerx_decode_host_window -> (rc, [(rc_k, w_k, h_k, [flat planes of frame_stride samples], info_k)]): the first
@@ -517,21 +512,15 @@ class Session:
         return [int(x) for x in out]
 
     def _feed(self, fn, n: int, slots, data: int, offsets, lens, out, sizes=None):
-        """one of the three feed calls, its per-frame host arrays packed here; -> (rc, rcs, ws, hs)"""
-        m = max(n, 1)
-        offs, ln = (_sz * m)(*[int(o) for o in offsets]), (_sz * m)(*[int(x) for x in lens])
-        sizes = sizes or [(0, 0)] * n
-        rcs, ws, hs = (C.c_int * m)(), (_sz * m)(*[int(s[0]) for s in sizes]), (_sz * m)(*[int(s[1]) for s in sizes])
-        rc = fn(self.handle, n, c_array(C.c_int, slots), data, offs, ln, out, rcs, ws, hs)
-        return rc, list(rcs)[:n], list(ws)[:n], list(hs)[:n]
+        """one of the three feed calls -> (rc, rcs, ws, hs)"""
+        slots = c_array(C.c_int, slots)
+        return _per_frame(n, offsets, lens, lambda offs, ln, rcs, ws, hs: fn(self.handle, n, slots, data, offs, ln, out, rcs, ws, hs), sizes)
 
     def feed_host(self, feeds, slots=None, sizes=None):
         """feeds: a list of byte strings in host memory, feed k for slot slots[k] (None: 0 .. n - 1); sizes: (w, h) per feed,
         used while the slot has seen no valid packet -> (rc, [(rc_k, w_k, h_k, [flat planes of frame_stride samples])])"""
         n, ch = len(feeds), self.channels
-        lens = [len(f) for f in feeds]
-        offs = [sum(lens[:k]) for k in range(n)]
-        blob = np.frombuffer(b"".join(feeds), dtype=np.uint8).copy() if sum(lens) else np.zeros(1, np.uint8)
+        blob, offs, lens = _pack(feeds)
         planes = [np.zeros(max(self.frame_stride, 1), np.uint16 if self.bits == 16 else np.uint8) for _ in range(n * ch)]
         ptrs = (C.c_void_p * max(n * ch, 1))(*[a.ctypes.data for a in planes])
         rc, rcs, ws, hs = self._feed(self.lib.icerx_session_feed_host, n, slots, blob.ctypes.data, offs, lens, ptrs, sizes)
@@ -554,12 +543,9 @@ class Session:
         _need_tensors(("data", data, torch.uint8), ("out", out, want))
         if out.numel() != n * self.channels * self.frame_stride:
             raise ValueError("out must hold n * channels * frame_stride samples")
+        stream_stride = _stream_stride(data, stream_stride, (offsets,))
         if offsets is None:
-            if stream_stride is None:
-                if data.dim() != 2:
-                    raise ValueError("a 1-D blob needs offsets or stream_stride")
-                stream_stride = data.stride(0)
-            offsets = [k * int(stream_stride) for k in range(n)]
+            offsets = [k * stream_stride for k in range(n)]
         if any(int(o) + int(x) > data.numel() for o, x in zip(offsets, lens)):
             raise ValueError("a feed leaves the blob")
         with torch.cuda.device(data.device):
