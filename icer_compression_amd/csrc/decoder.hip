@@ -635,9 +635,7 @@ int batch_chains(BatchRun &r, const BatchOut &out)
         }
         if (n_fast < nc) {
             // the planes of a segment side by side (one wavefront per chain) if the chain's row ring fits LDS
-            const size_t ring_bytes = route.rest_ring_elems * sizeof(uint16_t) + kStateBytes;
-            // (the kernel's static DecoderTables block counts against the same 64 KiB a launch gets without asking)
-            if (mode != 0 && ring_bytes + sizeof(DecoderTables) + 256u <= 65536u) {
+            if (mode != 0 && wave_ring_fits(route.rest_ring_elems)) {
                 if ((rc = ensure_side_streams(d)) != ICER_RESULT_OK) goto done;
                 // (everything the null stream did so far is complete: the upload of `chains` above was a blocking copy)
                 uint32_t from = n_fast;

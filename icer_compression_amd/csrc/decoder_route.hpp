@@ -33,6 +33,9 @@ ICER_HD bool takes_planes(const DRouteRule &r, const ChainDesc &c, uint32_t stre
 {
     return want_planes && c.fast && stream_len >= 4u && pw_lds_bytes(c.w, (int)r.nplanes) <= r.planes_lds_limit;
 }
+// may the lane-per-plane kernel take a row ring of this many elements?  Its per-lane state and its static DecoderTables block
+// count against the same 64 KiB a launch gets without asking.
+inline bool wave_ring_fits(size_t ring_elems) { return ring_elems * sizeof(uint16_t) + kStateBytes + sizeof(DecoderTables) + 256u <= 65536u; }
 
 // decode_batch's order of the chains of a call, and what its launches need to know of it
 constexpr int kRingClasses = 4;
@@ -57,20 +60,25 @@ struct BatchRoute {
 //   lane per plane   4: 107            16: 435       32: 922   64: 885-921   128: 1036
 // -- the cross-over lies near 20 streams = 12 chains per compute unit (24 streams by this rule: 686).  ICER_DEC_WAVE=2
 // pins the wave-per-plane kernel.
-// stream_len_of_frame(f): the bytes of the stream of frame f (ChainDesc::frame)
-template <class StreamLenOf>
-BatchRoute route_batch_chains(std::vector<ChainDesc> &chains, StreamLenOf stream_len_of_frame, bool want_planes, size_t planes_lds_limit, int nplanes)
+// stream_len_of_frame(f): the bytes of the stream of frame f (ChainDesc::frame).  The elements are chains or anything that
+// carries one (a decode session's runs, decoder_session.hpp): chain_of(element) -> const ChainDesc &.
+template <class T, class ChainOf, class StreamLenOf>
+BatchRoute route_batch_chains(std::vector<T> &chains, ChainOf chain_of, StreamLenOf stream_len_of_frame, bool want_planes, size_t planes_lds_limit,
+                              int nplanes)
 {
     BatchRoute r = {};
     const DRouteRule rule = {-1, (uint32_t)std::min<size_t>(planes_lds_limit, 0xFFFFFFFFu), 0u, (uint32_t)nplanes};
-    const auto rest = std::stable_partition(chains.begin(), chains.end(), [&](const ChainDesc &c) {
+    const auto rest = std::stable_partition(chains.begin(), chains.end(), [&](const T &e) {
+        const ChainDesc &c = chain_of(e);
         return takes_planes(rule, c, stream_len_of_frame(c.frame), want_planes); });
     r.n_fast = (uint32_t)(rest - chains.begin());
-    for (auto c = chains.begin(); c != rest; ++c) r.planes_lds = std::max(r.planes_lds, pw_lds_bytes(c->w, nplanes));
+    for (auto c = chains.begin(); c != rest; ++c) r.planes_lds = std::max(r.planes_lds, pw_lds_bytes(chain_of(*c).w, nplanes));
     // Longest chains first within either kernel's share (a chain's time goes with its samples): the level-1 chains of
     // every stream start at once, one or two per compute unit, and the short ones fill the gaps -- in stream order the
     // long chains of the later streams of a batch started when those of the first were half-way.
-    auto longer = [](const ChainDesc &a, const ChainDesc &b) { return (uint32_t)a.w * a.h > (uint32_t)b.w * b.h; };
+    auto longer = [&](const T &ea, const T &eb) {
+        const ChainDesc &a = chain_of(ea), &b = chain_of(eb);
+        return (uint32_t)a.w * a.h > (uint32_t)b.w * b.h; };
     std::stable_sort(chains.begin(), rest, longer);
     std::stable_sort(rest, chains.end(), longer);
     // The lane-per-plane kernel's share by size class of row ring (a launch reserves the LDS of its widest chain for every
@@ -78,20 +86,27 @@ BatchRoute route_batch_chains(std::vector<ChainDesc> &chains, StreamLenOf stream
     // of level 2 and 28 of level 3): class k = rings of at most limit >> k bytes, widest class first, each class a launch
     // of its own on a stream of its own, all of them side by side.
     r.rest_ring_elems = 2;
-    for (auto c = rest; c != chains.end(); ++c) r.rest_ring_elems = std::max(r.rest_ring_elems, ring_elems_for(c->w, nplanes));
-    auto cls = [&](const ChainDesc &c) {
-        const size_t e = ring_elems_for(c.w, nplanes);
+    for (auto c = rest; c != chains.end(); ++c) r.rest_ring_elems = std::max(r.rest_ring_elems, ring_elems_for(chain_of(*c).w, nplanes));
+    auto cls = [&](const T &x) {
+        const size_t e = ring_elems_for(chain_of(x).w, nplanes);
         int k = 0;
         while (k + 1 < kRingClasses && e * 2u <= (r.rest_ring_elems >> k)) k++;
         return k;
     };
-    std::stable_sort(rest, chains.end(), [&](const ChainDesc &a, const ChainDesc &b) { return cls(a) < cls(b); });
+    std::stable_sort(rest, chains.end(), [&](const T &a, const T &b) { return cls(a) < cls(b); });
     auto at = rest;
     for (int k = 0; k < kRingClasses; k++) {
-        for (r.class_elems[k] = 2; at != chains.end() && cls(*at) == k; ++at) r.class_elems[k] = std::max(r.class_elems[k], ring_elems_for(at->w, nplanes));
+        for (r.class_elems[k] = 2; at != chains.end() && cls(*at) == k; ++at)
+            r.class_elems[k] = std::max(r.class_elems[k], ring_elems_for(chain_of(*at).w, nplanes));
         r.class_end[k] = (uint32_t)(at - chains.begin());
     }
     return r;
+}
+template <class StreamLenOf>
+BatchRoute route_batch_chains(std::vector<ChainDesc> &chains, StreamLenOf stream_len_of_frame, bool want_planes, size_t planes_lds_limit, int nplanes)
+{
+    return route_batch_chains(chains, [](const ChainDesc &c) -> const ChainDesc & { return c; }, stream_len_of_frame, want_planes, planes_lds_limit,
+                              nplanes);
 }
 
 }  // namespace icer

@@ -7,15 +7,18 @@
 //   1. finds and checks the feed's packets (batch_packets) and walks them on the host by the decoder's cursor rule;
 //   2. accepts, per chain, the planes that continue what the slot holds (session_accept) and plans the slot with a table whose
 //      held planes read kHeldPlane (plan_chains: the chains, levels and rc of the plain decode of everything accepted so far);
-//   3. runs the chains that have new planes, in place on the state planes: the wave-per-plane kernel with a loader wave
-//      (pw_run_chain_resume) for chains that are `fast` and fit its LDS, one thread per chain (decode_chain_resume) for the
-//      rest, which also reports where a chain stopped;
+//   3. runs the chains that have new planes, in place on the state planes, routed like the plain decode (decoder_route.hpp;
+//      ICER_DEC_WAVE = 0 / 1 / 2 pins a kernel): while the call's fast chains are at most 12 per compute unit, the wave-per-plane
+//      kernel with a loader wave (pw_run_chain_resume) for chains that are `fast` and fit its LDS; above that load, and for every
+//      chain under ICER_DEC_WAVE=1, the lane-per-plane kernel over a row ring that starts out holding the held words
+//      (decode_chain_wave_resume) where the ring fits LDS; one thread per chain (decode_chain_resume) for what is left.  The last
+//      two report where a chain stopped;
 //   4. copies the fed slots' planes into the working buffer and runs batch_samples / batch_results on the copy as they are,
 //      with the fed slots' chain table in d->chains for reconstruct_kernel (it counts planes from the top while
 //      pkt != kNoPacket, so held planes count).
 // Can a plane of the wave-per-plane kernel fail?  No: pw_decode_bin has no failing exit, as entropy_decode_fast has none -- every
 // length test of the reference compares at most 11 bits with the packet's length, and the kernel takes packets of
-// >= kFastPacketBits only.  So only the thread-per-chain kernel writes a status word.
+// >= kFastPacketBits only.  So only the other two kernels write a status word.
 #pragma once
 
 namespace {
@@ -61,6 +64,22 @@ decode_chains_planes_resume_kernel(uint16_t *state, size_t frame_stride, int cha
 #endif
     (void)pw_run_chain_resume(lds, wave, c, nplanes, sign_bit, state + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w,
                               data + f.stream_off, f.stream_len, tables, err);
+}
+
+// one wavefront per chain and one lane per NEW bit plane, over a row ring that holds the held words (decode_chain_wave_resume);
+// launch shape and LDS as decode_chains_wave_kernel, lowest_ok[chain of the launch]: decode_chain_resume
+__global__ void __launch_bounds__(64)
+decode_chains_wave_resume_kernel(uint16_t *state, size_t frame_stride, int channels, const ChainDesc *__restrict__ chains,
+                                 const uint8_t *__restrict__ data, const FrameInfo *__restrict__ frames,
+                                 const DecoderTables *__restrict__ tables, int nplanes, int sign_bit, uint32_t *__restrict__ lowest_ok)
+{
+    ICER_DYNAMIC_LDS(uint8_t, lds);                       // the lanes' per-bin arrays, then the chain's row ring
+    ICER_LDS_TABLES(lt, tables);
+    const ChainDesc c = chains[blockIdx.x];
+    const FrameInfo f = frames[c.frame];
+    uint16_t *ring = reinterpret_cast<uint16_t *>(lds + kStateBytes);
+    decode_chain_wave_resume(ring, state + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband, data + f.stream_off,
+                             f.stream_len, lt, nplanes, sign_bit, nullptr, lds, lowest_ok + blockIdx.x);
 }
 
 // the w * h words of every channel of row k's slot into row k of the working planes (grid.y = row * channels + channel)
@@ -203,8 +222,8 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
     std::vector<ChainDesc> recon, upload;
     std::vector<FrameInfo> by_slot((size_t)s->n_slots);
     std::vector<uint32_t> slot_of_row((size_t)n), lowest;
-    uint32_t n_fast = 0, nc = 0;
-    size_t planes_lds = 0, at = 0;
+    uint32_t n_fast = 0, n_ring = 0, nc = 0;        // runs [0, n_fast): wave per plane; [n_fast, n_ring): lane per plane; [n_ring, nc): threads
+    size_t at = 0;
     int rc = batch_packets(r, data, data_on_device);
     if (rc != ICER_RESULT_OK) return rc;
     *touched = true;
@@ -226,21 +245,37 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
     // (a slot that delivers nothing -- no samples, or a plan that stopped before its first chain -- has no chain here)
     runs.erase(std::remove_if(runs.begin(), runs.end(), [&](const SessionRun &x) { return by_slot[(size_t)x.slot].w == 0u; }), runs.end());
     if (!runs.empty()) {
+        // Which kernel takes a run: the plain decode's rule (decoder_route.hpp).  The wave-per-plane kernel by load (dwant_planes),
+        // for the chains it can take (takes_planes); of the others the lane-per-plane kernel those whose ring fits, by ring class on
+        // the side streams, and one thread per chain what is left.  One thing is kept from before the load rule: while the planes
+        // kernel is the choice by load (ICER_DEC_WAVE unset), the chains it leaves -- short packets, few and small -- stay on the
+        // thread route, so a feed below the threshold takes the kernels it always took.
         const int mode = dec_wave_mode();
-        const bool want_planes = mode != 0 && mode != 1 && d->tables.lut_ok != 0u;
+        uint32_t n_eligible = 0;
+        for (const SessionRun &x : runs) n_eligible += x.c.fast ? 1u : 0u;
+        const bool want_planes = dwant_planes(mode, d->tables.lut_ok, n_eligible, (uint32_t)d->n_cus);
+        const bool want_lanes = mode != 0 && !(mode == -1 && want_planes);
         // (the dynamic LDS the resume planes kernel may take: the decoder's figure, granted to this kernel too)
         const size_t lds_limit = grant_dynamic_lds(reinterpret_cast<const void *>(decode_chains_planes_resume_kernel), resolve_planes_lds(d), &s->lds_state);
         const DRouteRule rule = {mode, (uint32_t)std::min<size_t>(lds_limit, 0xFFFFFFFFu), 0u, (uint32_t)nplanes};
-        // the routing rule of the plain decode (takes_planes), whatever the load; longest chains first within either share
-        const auto rest = std::stable_partition(runs.begin(), runs.end(), [&](const SessionRun &x) {
-            return takes_planes(rule, x.c, by_slot[(size_t)x.slot].stream_len, want_planes); });
-        auto longer = [](const SessionRun &a, const SessionRun &b) { return (uint32_t)a.c.w * a.c.h > (uint32_t)b.c.w * b.c.h; };
-        std::stable_sort(runs.begin(), rest, longer);
-        std::stable_sort(rest, runs.end(), longer);
-        n_fast = (uint32_t)(rest - runs.begin()); nc = (uint32_t)runs.size();
+        auto stream_len_of = [&](uint32_t slot) { return by_slot[(size_t)slot].stream_len; };       // (a run's chain names its slot as its frame)
+        // the thread route's share goes to the back, longest first; the rest in the order and the classes of the plain decode
+        const auto slow = std::stable_partition(runs.begin(), runs.end(), [&](const SessionRun &x) {
+            return takes_planes(rule, x.c, stream_len_of(x.c.frame), want_planes) || (want_lanes && wave_ring_fits(ring_elems_for(x.c.w, nplanes))); });
+        std::vector<SessionRun> threads(slow, runs.end());
+        runs.erase(slow, runs.end());
+        std::stable_sort(threads.begin(), threads.end(), [](const SessionRun &a, const SessionRun &b) { return (uint32_t)a.c.w * a.c.h > (uint32_t)b.c.w * b.c.h; });
+        const BatchRoute route = route_batch_chains(runs, [](const SessionRun &x) -> const ChainDesc & { return x.c; }, stream_len_of, want_planes,
+                                                    lds_limit, nplanes);
+        n_fast = route.n_fast; n_ring = (uint32_t)runs.size();
+        runs.insert(runs.end(), threads.begin(), threads.end());
+        nc = (uint32_t)runs.size();
         for (const SessionRun &x : runs) upload.push_back(x.c);
-        for (uint32_t i = 0; i < n_fast; i++) planes_lds = std::max(planes_lds, pw_lds_bytes(runs[i].c.w, nplanes));
         const DecoderTables *tables = (const DecoderTables *)d->dtables.p;
+        if (n_fast < nc) {                                      // a status word per chain of the two routes that report where a chain stopped
+            HIP_TRY(ensure(s->status, sizeof(uint32_t) * (nc - n_fast)));
+            HIP_TRY(hipMemset(s->status.p, 0, sizeof(uint32_t) * (nc - n_fast)));
+        }
         HIP_TRY(ensure(s->frames, sizeof(FrameInfo) * by_slot.size()));
         HIP_TRY(hipMemcpy(s->frames.p, by_slot.data(), sizeof(FrameInfo) * by_slot.size(), hipMemcpyHostToDevice));
         HIP_TRY(ensure(s->chains, sizeof(ChainDesc) * nc));
@@ -248,17 +283,34 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
         const ChainDesc *d_chains = (const ChainDesc *)s->chains.p;
         if (n_fast) {
             HIP_TRY(planes_err_begin(d));
-            ICER_LAUNCH_PLANES(decode_chains_planes_resume_kernel, n_fast, planes_lds, (uint16_t *)s->state.p, s->frame_stride, channels, d_chains,
+            ICER_LAUNCH_PLANES(decode_chains_planes_resume_kernel, n_fast, route.planes_lds, (uint16_t *)s->state.p, s->frame_stride, channels, d_chains,
                                r.d_data, (const FrameInfo *)s->frames.p, tables, nplanes, sign_bit, (uint32_t *)d->err.p);
             HIP_TRY(hipGetLastError());
         }
-        if (n_fast < nc) {
-            HIP_TRY(ensure(s->status, sizeof(uint32_t) * (nc - n_fast)));
-            HIP_TRY(hipMemset(s->status.p, 0, sizeof(uint32_t) * (nc - n_fast)));
-            ICER_LAUNCH(decode_chains_resume_kernel, (nc - n_fast + 63u) / 64u, 64, plane_block_bytes(64u), (uint16_t *)s->state.p, s->frame_stride,
-                        channels, d_chains + n_fast, nc - n_fast, r.d_data, (const FrameInfo *)s->frames.p, tables, nplanes, sign_bit,
-                        (uint32_t *)s->status.p);
+        if (n_fast < n_ring) {
+            if ((rc = ensure_side_streams(d)) != ICER_RESULT_OK) goto done;
+            // (everything the null stream did so far is complete: the upload of the chains above was a blocking copy)
+            uint32_t from = n_fast;
+            for (int k = 0; k < kRingClasses; from = route.class_end[k++]) {
+                if (route.class_end[k] == from) continue;
+                ICER_LAUNCH_WAVE_ON(d->side[k], decode_chains_wave_resume_kernel, route.class_end[k] - from,
+                                    route.class_elems[k] * sizeof(uint16_t) + kStateBytes, (uint16_t *)s->state.p, s->frame_stride, channels,
+                                    d_chains + from, r.d_data, (const FrameInfo *)s->frames.p, tables, nplanes, sign_bit,
+                                    (uint32_t *)s->status.p + (from - n_fast));
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        if (n_ring < nc) {
+            ICER_LAUNCH(decode_chains_resume_kernel, (nc - n_ring + 63u) / 64u, 64, plane_block_bytes(64u), (uint16_t *)s->state.p, s->frame_stride,
+                        channels, d_chains + n_ring, nc - n_ring, r.d_data, (const FrameInfo *)s->frames.p, tables, nplanes, sign_bit,
+                        (uint32_t *)s->status.p + (n_ring - n_fast));
             HIP_TRY(hipGetLastError());
+        }
+#ifndef ICER_HOST_MOCK
+        if (n_fast < n_ring)
+            for (hipStream_t st : d->side) HIP_TRY(hipStreamSynchronize(st));
+#endif
+        if (n_fast < nc) {
             lowest.resize(nc - n_fast);
             HIP_TRY(hipMemcpy(lowest.data(), s->status.p, sizeof(uint32_t) * (nc - n_fast), hipMemcpyDeviceToHost));
         }
@@ -268,8 +320,8 @@ int session_feed_run(icerx_session *s, BatchRun &r, const int *slot_of, const ui
             int last = x.lo;                                    // the lowest plane that was started
             if (i < n_fast) s->stats[0] += x.hi + 1 < nplanes ? 1u : 0u;
             else {
-                s->stats[1]++;
-                const int ok = (int)lowest[i - n_fast];         // (decode_chain_resume: the lowest plane held or ended kOk)
+                s->stats[1] += i >= n_ring ? 1u : 0u;
+                const int ok = (int)lowest[i - n_fast];         // (either route: the lowest plane held or ended kOk)
                 if (ok > x.lo) {                                // plane ok - 1 failed: the chain has stopped, what lay below never started
                     icerx_session::Slot &sl = s->slots[(size_t)x.slot];
                     last = ok - 1;

@@ -42,6 +42,12 @@
  * ws, hs are per fed frame; the in-values of ws and hs are used only while the slot has seen no valid packet.  A call that
  * returns ICER_FATAL_ERROR (icerx_decoder_last_error) has reset the slots it was feeding.
  *
+ * Which kernel runs a chain.  A feed routes like the plain decode and honours ICER_DEC_WAVE, read at every feed: unset, the
+ * chains whose packets all take the fast entropy path run in the wave-per-plane kernel while the call brings at most 12 of them
+ * per compute unit (the others, chains with a packet below 16 bits, then take one thread each), and above that load every
+ * chain runs in the lane-per-plane kernel, which resumes over a row ring loaded from the state; 0 pins one thread per chain, 1 the lane-per-plane kernel, 2 the wave-per-plane kernel where it applies.  A chain
+ * whose ring does not fit the lane-per-plane kernel's LDS runs on a thread.  The images do not depend on the route.
+ *
  * Not here: the stream-ordered, device-planned twin (*_async) -- the next step, which wants the chain table on the device --
  * and window sessions. */
 #ifndef ICER_HIP_DEC_SESSION_H

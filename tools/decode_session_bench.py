@@ -11,7 +11,9 @@ and the master, the increments between them come from Recutter.combine (DIFFEREN
 turns: the session is reset, then per rung the increment is fed (Session.feed_torch: icerx_session_feed_device) and the rung's
 whole stream is decoded by the plain call (Decoder.decode_device: icerx_decode_device, which this feature leaves alone) -- each
 timed around call + synchronise.  Median, minimum and maximum over `--reps` rounds after `--warmup` untimed ones.  Checked in the
-same run: every feed's planes equal the plain call's.  One JSON line."""
+same run: every feed's planes equal the plain call's.  After the timed rounds two untimed ones count, per rung, the chains by route
+(`routes`): one pinned to the thread route (ICER_DEC_WAVE=0), where icerx_session_stats counts every chain of a feed, and one in
+the mode of the run.  One JSON line."""
 import argparse
 import json
 import os
@@ -79,12 +81,45 @@ def main():
                     times[("plain", i)].append(t_plain)
                 same = same and bool(torch.equal(fed, plain))
         stats = ses.stats()
+
+        def chain_counts(mode):
+            """per rung (chains resumed in the wave-per-plane kernel, chains on the thread route) of one untimed round under ICER_DEC_WAVE=mode"""
+            keep = os.environ.get("ICER_DEC_WAVE")
+            if mode is None:
+                os.environ.pop("ICER_DEC_WAVE", None)
+            else:
+                os.environ["ICER_DEC_WAVE"] = mode
+            try:
+                ses.reset()
+                out = []
+                for i in range(4):
+                    before = ses.stats()
+                    ses.feed_torch(d_incs[i], [len(incs[i])] * n, fed, offsets=[k * len(incs[i]) for k in range(n)])
+                    torch.cuda.synchronize()
+                    out.append((ses.stats()[0] - before[0], ses.stats()[1] - before[1]))
+                return out
+            finally:
+                os.environ.pop("ICER_DEC_WAVE", None)
+                if keep is not None:
+                    os.environ["ICER_DEC_WAVE"] = keep
+
+        # the share of chains by route: pinned to the thread route every chain of a feed is counted, in the mode of this run the
+        # chains resumed behind a loader wave and those on the thread route are; what is left took the lane-per-plane kernel, or
+        # the wave-per-plane kernel with nothing held (only the rung fed into an empty slot has such chains)
+        total, own = chain_counts("0"), chain_counts(os.environ.get("ICER_DEC_WAVE") or None)
+        routes = []
+        for i in range(4):
+            chains, (resumed, threads) = total[i][1], own[i]
+            left = chains - resumed - threads
+            routes.append({"chains": chains, "wave_per_plane_resumed": resumed, "thread_per_chain": threads,
+                           "lane_per_plane_or_nothing_held": left,
+                           "shares": [round(x / max(chains, 1), 4) for x in (resumed, threads, left)]})
         ses.close()
         dec.close()
         row = lambda v: {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3)}
         return {"frames": n, "size": [w, h], "stages": stages, "segments": segments, "parity": same,
                 "rungs": [{"rung": ("q", "2q", "4q", "lossless")[i], "stream_bytes": len(rungs[i]), "increment_bytes": len(incs[i]),
-                           "feed": row(times[("feed", i)]), "plain_decode_of_the_rung": row(times[("plain", i)])} for i in range(4)],
+                           "feed": row(times[("feed", i)]), "plain_decode_of_the_rung": row(times[("plain", i)]), "routes": routes[i]} for i in range(4)],
                 "session_stats": dict(zip(("chains_resumed_wave_per_plane", "chains_thread_per_chain", "planes_decoded", "packets_dropped"), stats))}
 
     line = {"metric": "decode session: time of a feed beside the plain decode of the same rung", "unit": "ms", "reps": a.reps, "warmup": a.warmup,
