@@ -127,7 +127,7 @@ decode_chains_kernel(uint16_t *__restrict__ planes, size_t frame_stride, int cha
     const FrameInfo f = frames[c.frame];
     PlaneDecoder job;
     plane_attach_columns(job, state, 64u, threadIdx.x);
-    decode_chain(job, planes + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband, data + f.stream_off,
+    decode_chain(job, chain_plane(planes, c, channels, frame_stride), f.w, c, (int)c.subband, data + f.stream_off,
                  f.stream_len, lt, nplanes, sign_bit);
 }
 
@@ -143,8 +143,32 @@ decode_chains_wave_kernel(uint16_t *__restrict__ planes, size_t frame_stride, in
     const ChainDesc c = chains[blockIdx.x];
     const FrameInfo f = frames[c.frame];
     uint16_t *ring = reinterpret_cast<uint16_t *>(lds + kStateBytes);
-    decode_chain_wave(ring, planes + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband,
+    decode_chain_wave(ring, chain_plane(planes, c, channels, frame_stride), f.w, c, (int)c.subband,
                       data + f.stream_off, f.stream_len, lt, nplanes, sign_bit, nullptr, lds);
+}
+
+// A workgroup of a planes kernel takes up chain `c`: control words, zero row and ring start out zero; and every wave's number,
+// as a scalar.  (The CPU mock runs a chain's waves in turns inside one call, which clears the block itself.)  Two helpers, not
+// one: planes_list_kernel takes the wave number once, in front of its loop over chains, and moving it into the loop changes
+// that kernel's code.
+ICER_DEV void pw_workgroup_clear(uint8_t *lds, const ChainDesc &c, int nplanes)
+{
+#ifndef ICER_HOST_MOCK
+    uint32_t *w = reinterpret_cast<uint32_t *>(lds);
+    const uint32_t words = (uint32_t)((pw_lds_bytes(c.w, nplanes) + 3u) / 4u);
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) w[i] = 0;
+    __syncthreads();
+#else
+    (void)lds; (void)c; (void)nplanes;
+#endif
+}
+ICER_DEV uint32_t pw_workgroup_wave()
+{
+#ifndef ICER_HOST_MOCK
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#else
+    return 0;
+#endif
 }
 
 // one wavefront per bit plane, wave-uniform decisions (decoder_planes.hpp): grid = chains that take the fast entropy path,
@@ -158,18 +182,9 @@ decode_chains_planes_kernel(uint16_t *__restrict__ planes, size_t frame_stride, 
     ICER_DYNAMIC_LDS(uint8_t, lds);
     const ChainDesc &c = chains[blockIdx.x];                  // (read in place: see pw_run_chain)
     const FrameInfo f = frames[c.frame];
-#ifndef ICER_HOST_MOCK
-    {   // control words, zero row and ring start out zero
-        uint32_t *w = reinterpret_cast<uint32_t *>(lds);
-        const uint32_t words = (uint32_t)((pw_lds_bytes(c.w, nplanes) + 3u) / 4u);
-        for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) w[i] = 0;
-        __syncthreads();
-    }
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
-    const uint32_t wave = 0;
-#endif
-    (void)pw_run_chain(lds, wave, c, nplanes, sign_bit, planes + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w,
+    pw_workgroup_clear(lds, c, nplanes);
+    const uint32_t wave = pw_workgroup_wave();
+    (void)pw_run_chain(lds, wave, c, nplanes, sign_bit, chain_plane(planes, c, channels, frame_stride), f.w,
                        data + f.stream_off, f.stream_len, tables, err);
 }
 

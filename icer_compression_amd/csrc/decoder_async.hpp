@@ -401,24 +401,13 @@ planes_list_kernel(uint16_t *__restrict__ planes, size_t frame_stride, int chann
 {
     ICER_DYNAMIC_LDS(uint8_t, lds);
     const uint32_t n = head->count[0], start = head->start[0];
-#ifndef ICER_HOST_MOCK
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
-    const uint32_t wave = 0;
-#endif
+    const uint32_t wave = pw_workgroup_wave();
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
         const ChainDesc &c = chains[lists[start + i]];
         const FrameInfo f = frames[c.frame];
-#ifndef ICER_HOST_MOCK
-        __syncthreads();                                     // (every wave is done with the previous chain's LDS)
-        {
-            uint32_t *w = reinterpret_cast<uint32_t *>(lds);
-            const uint32_t words = (uint32_t)((pw_lds_bytes(c.w, nplanes) + 3u) / 4u);
-            for (uint32_t t = threadIdx.x; t < words; t += blockDim.x) w[t] = 0;
-            __syncthreads();
-        }
-#endif
-        (void)pw_run_chain(lds, wave, c, nplanes, sign_bit, planes + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w,
+        ICER_BARRIER();                                      // (every wave is done with the previous chain's LDS)
+        pw_workgroup_clear(lds, c, nplanes);
+        (void)pw_run_chain(lds, wave, c, nplanes, sign_bit, chain_plane(planes, c, channels, frame_stride), f.w,
                            data + f.stream_off, f.stream_len, tables, ferr + c.frame);
     }
 }
@@ -436,7 +425,7 @@ wave_list_kernel(uint16_t *__restrict__ planes, size_t frame_stride, int channel
         const ChainDesc c = chains[lists[start + i]];
         const FrameInfo f = frames[c.frame];
         ICER_BARRIER();
-        decode_chain_wave(ring, planes + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband,
+        decode_chain_wave(ring, chain_plane(planes, c, channels, frame_stride), f.w, c, (int)c.subband,
                           data + f.stream_off, f.stream_len, lt, nplanes, sign_bit, nullptr, lds);
     }
 }
@@ -454,7 +443,7 @@ thread_list_kernel(uint16_t *__restrict__ planes, size_t frame_stride, int chann
         const FrameInfo f = frames[c.frame];
         PlaneDecoder job;
         plane_attach_columns(job, state, 64u, threadIdx.x);
-        decode_chain(job, planes + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband,
+        decode_chain(job, chain_plane(planes, c, channels, frame_stride), f.w, c, (int)c.subband,
                      data + f.stream_off, f.stream_len, lt, nplanes, sign_bit);
     }
 }

@@ -99,6 +99,11 @@ struct ChainDesc {
     uint32_t fast;              // every packet the chain runs has >= kFastPacketBits bits: none of the reference's length tests
                                 // can fire, the chain may take the wave-per-plane kernel (decoder_planes.hpp)
 };
+// the channel plane a chain lives in: plane `chan` of frame `frame`, frame_stride words each, rows of the frame's width
+ICER_HD uint16_t *chain_plane(uint16_t *planes, const ChainDesc &c, int channels, size_t frame_stride)
+{
+    return planes + ((size_t)c.frame * channels + c.chan) * frame_stride;
+}
 
 // ------------------------------------------------------------------------------------------ entropy decoder
 struct EntropyDecoder {
@@ -672,30 +677,18 @@ ICER_HD uint32_t packet_bits(const uint8_t *stream, uint32_t at)
 
 // all planes of one chain, top plane first, until one is missing or fails (icer_partition.c:427-443)
 // `p`: a plane job with its storage attached (plane_attach_local / plane_attach_columns); it is reused plane after plane
-ICER_HD void decode_chain(PlaneDecoder &p, uint16_t *plane, size_t stride, const ChainDesc &c, int subband, const uint8_t *stream,
-                          uint32_t stream_len, const DecoderTables &t, int planes, int sign_bit)
-{
-    for (int lsb = planes - 1; lsb >= 0; lsb--) {
-        const uint32_t at = c.pkt[lsb];
-        if (at == kNoPacket) break;
-        entropy_init(p.d, stream, stream_len, at + (uint32_t)kHeaderBytes, packet_bits(stream, at));
-        plane_begin(p, lsb, sign_bit, c.w, c.h);
-        while (p.status == 1) plane_step(p, plane + c.first, c.w, c.h, stride, subband, sign_bit, t);
-        if (p.status != kOk) break;
-    }
-}
-
-// The same for a chain of a decode session: the planes marked kHeldPlane are in `plane` already (nothing else of a plane
+// kResume: a chain of a decode session.  The planes marked kHeldPlane are in `plane` already (nothing else of a plane
 // outlives it: a packet's context model starts fresh), so resuming is starting the loop at the first plane that has a packet.
-// *lowest_ok: the lowest plane that is held or ended kOk (`planes`: none) -- the host learns from it where a chain stopped.
-ICER_HD void decode_chain_resume(PlaneDecoder &p, uint16_t *plane, size_t stride, const ChainDesc &c, int subband, const uint8_t *stream,
-                                 uint32_t stream_len, const DecoderTables &t, int planes, int sign_bit, uint32_t *lowest_ok)
+// *lowest_ok (kResume only): the lowest plane that is held or ended kOk (`planes`: none) -- where the chain stopped, for the host.
+template <bool kResume>
+ICER_HD void decode_chain_body(PlaneDecoder &p, uint16_t *plane, size_t stride, const ChainDesc &c, int subband, const uint8_t *stream,
+                               uint32_t stream_len, const DecoderTables &t, int planes, int sign_bit, uint32_t *lowest_ok)
 {
     int ok = planes;
     for (int lsb = planes - 1; lsb >= 0; lsb--) {
         const uint32_t at = c.pkt[lsb];
         if (at == kNoPacket) break;
-        if (at != kHeldPlane) {
+        if (!kResume || at != kHeldPlane) {
             entropy_init(p.d, stream, stream_len, at + (uint32_t)kHeaderBytes, packet_bits(stream, at));
             plane_begin(p, lsb, sign_bit, c.w, c.h);
             while (p.status == 1) plane_step(p, plane + c.first, c.w, c.h, stride, subband, sign_bit, t);
@@ -703,7 +696,17 @@ ICER_HD void decode_chain_resume(PlaneDecoder &p, uint16_t *plane, size_t stride
         }
         ok = lsb;
     }
-    *lowest_ok = (uint32_t)ok;
+    if (kResume) *lowest_ok = (uint32_t)ok;
+}
+ICER_HD void decode_chain(PlaneDecoder &p, uint16_t *plane, size_t stride, const ChainDesc &c, int subband, const uint8_t *stream,
+                          uint32_t stream_len, const DecoderTables &t, int planes, int sign_bit)
+{
+    decode_chain_body<false>(p, plane, stride, c, subband, stream, stream_len, t, planes, sign_bit, nullptr);
+}
+ICER_HD void decode_chain_resume(PlaneDecoder &p, uint16_t *plane, size_t stride, const ChainDesc &c, int subband, const uint8_t *stream,
+                                 uint32_t stream_len, const DecoderTables &t, int planes, int sign_bit, uint32_t *lowest_ok)
+{
+    decode_chain_body<true>(p, plane, stride, c, subband, stream, stream_len, t, planes, sign_bit, lowest_ok);
 }
 
 // ---- the planes of a chain side by side.  Plane lsb reads, of the plane above, the samples to the right and in the

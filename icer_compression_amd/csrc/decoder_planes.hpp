@@ -507,35 +507,16 @@ ICER_DEV void pw_init_resume(PlaneWave &p, uint32_t j, const PwResume &s, const 
     else pw_init_at(p, j, s.nrun, (uint32_t)planes - s.held - j - (s.held ? 0u : 1u), c, planes, sign_bit, plane, stride, stream, stream_len, t);
 }
 
-
 // All planes of one chain: the body of decode_chains_planes_kernel.  GPU build: called by every wavefront of the workgroup
 // (wave `wave` of kPwWaves; `lds` = pw_lds_bytes(c.w, planes) bytes, zeroed by the workgroup before); a wave that waits
 // longer than kPwSpinLimit polls gives up and raises *err (the host then fails the call loudly) -- never a hang.
 // CPU builds (tests only): one call runs the chain's waves in turns.  Returns false on a lock-up / time-out.
 constexpr uint32_t kPwSpinLimit = 1u << 20;       // (polls; the late ones sleep 8 k cycles each: seconds)
 #ifdef ICER_WAVE_EMU
-ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t /*wave*/, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
-                           const uint8_t *stream, uint32_t stream_len, const DecoderTables *t, uint32_t * /*err*/)
-{
-    memset(lds, 0, pw_lds_bytes(c.w, planes));
-    PwShared &sh = *reinterpret_cast<PwShared *>(lds);
-    uint16_t *zero_row = reinterpret_cast<uint16_t *>(lds + sizeof(PwShared)), *ring = zero_row + pw_ring_pitch(c.w);
-    uint32_t nrun = 0;
-    while ((int)nrun < planes && c.pkt[planes - 1 - (int)nrun] != kNoPacket) nrun++;
-    PlaneWave pw[kPlanes];
-    for (uint32_t j = 0; j < nrun; j++) pw_init(pw[j], j, nrun, c, planes, sign_bit, plane, stride, stream, stream_len, t);
-    for (;;) {
-        bool progress = false, all_done = true;
-        for (uint32_t j = 0; j < nrun; j++) {
-            const int st = pw_step(pw[j], sh, zero_row, ring);
-            progress = progress || st == 1;
-            all_done = all_done && (st == 2 || pw[j].r >= pw[j].h);
-        }
-        if (all_done) return true;
-        if (!progress) return false;
-    }
-}
-// the same for a chain of a decode session (pw_resume_shape): the loader in wave 0's place when planes are held
+// One turn-taking runner, that of a chain of a decode session (pw_resume_shape): the loader in wave 0's place when planes are
+// held.  A plain chain runs it as it is, and exactly: its table has no kHeldPlane mark, so held = 0 and nrun = fresh = the
+// packets from the top down to the first kNoPacket; pw_init_resume then gives wave j plane planes - 1 - j, as pw_init does;
+// and there is no loader, every wave takes pw_step.
 ICER_DEV bool pw_run_chain_resume(uint8_t *lds, uint32_t /*wave*/, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
                                   const uint8_t *stream, uint32_t stream_len, const DecoderTables *t, uint32_t * /*err*/)
 {
@@ -556,6 +537,11 @@ ICER_DEV bool pw_run_chain_resume(uint8_t *lds, uint32_t /*wave*/, const ChainDe
         if (!progress) return false;
     }
 }
+ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t wave, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
+                           const uint8_t *stream, uint32_t stream_len, const DecoderTables *t, uint32_t *err)
+{
+    return pw_run_chain_resume(lds, wave, c, planes, sign_bit, plane, stride, stream, stream_len, t, err);
+}
 #else
 // One wave's share of a chain: its steps (kLoader: pw_load_step, else pw_step), each behind the wait for what it needs.
 // (the loop must leave by wave-UNIFORM conditions only -- the lane-0 store of the error word comes after it: a per-lane
@@ -566,25 +552,34 @@ ICER_DEV bool pw_run_chain_resume(uint8_t *lds, uint32_t /*wave*/, const ChainDe
 // what the block needs is computed once (pw_wait_for), a poll is a load, a compare and a sleep -- and the sleep grows
 // with the time waited: 128 cycles for the first polls (a neighbour about to publish), then 1 k, then 8 k cycles.  A
 // long sleep costs a waiting wave nothing: it waits because it is the faster one of a pair and has a row of slack.
+// The loop is TEXT (it declares `ok`; p, sh, err are the caller's), because pw_run_chain has to hold it in its own body: every
+// kernel's code is pinned (profiles/decode_session.md), and as a call the loop compiles differently there.  Tried and rejected:
+//   (a) pw_run_chain calls pw_wave_loop<false>: planes_list_kernel 52 -> 53 VGPRs, accum_offset 52 -> 56, and the code of
+//       decode_chains_planes_kernel changes;
+//   (b) one template <bool kResume> runner, the wait loop written once, a wave-uniform `loader` flag: the plain kernels keep
+//       their figures but not their code, decode_chains_planes_resume_kernel 46 -> 68 VGPRs.
+#define PW_WAVE_LOOP(STEP)                                                                                                       \
+    bool ok = true;                                                                                                              \
+    while (p.r < p.h) {                                                                                                          \
+        uint32_t need;                                                                                                           \
+        const uint32_t *word = pw_wait_for(p, sh, &need);                                                                        \
+        uint32_t spins = 0;                                                                                                      \
+        while (PW_UNIFORM(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) {                     \
+            if (spins < 6u) __builtin_amdgcn_s_sleep(2);                                                                         \
+            else if (spins < 12u) __builtin_amdgcn_s_sleep(16);                                                                  \
+            else __builtin_amdgcn_s_sleep(127);                                                                                  \
+            spins++;                                                                                                             \
+            if (spins > kPwSpinLimit ||                                                                                          \
+                ((spins & 63u) == 0u && PW_UNIFORM(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u)) { ok = false; break; } \
+        }                                                                                                                        \
+        if (!ok) break;                                                                                                          \
+        if ((STEP) == 0) { ok = false; break; }     /* (cannot be: the condition just held and only grows) */                    \
+    }                                                                                                                            \
+    if (!ok && (threadIdx.x & 63u) == 0u) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 template <bool kLoader>
 ICER_DEV bool pw_wave_loop(PlaneWave &p, PwShared &sh, uint16_t *zero_row, uint16_t *ring, uint32_t *err)
 {
-    bool ok = true;
-    while (p.r < p.h) {
-        uint32_t need;
-        const uint32_t *word = pw_wait_for(p, sh, &need);
-        uint32_t spins = 0;
-        while (PW_UNIFORM(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) {
-            if (spins < 6u) __builtin_amdgcn_s_sleep(2);
-            else if (spins < 12u) __builtin_amdgcn_s_sleep(16);
-            else __builtin_amdgcn_s_sleep(127);
-            spins++;
-            if (spins > kPwSpinLimit || ((spins & 63u) == 0u && PW_UNIFORM(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u)) { ok = false; break; }
-        }
-        if (!ok) break;
-        if ((kLoader ? pw_load_step(p, sh, ring) : pw_step(p, sh, zero_row, ring)) == 0) { ok = false; break; }     // (cannot be: the condition just held and only grows)
-    }
-    if (!ok && (threadIdx.x & 63u) == 0u) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    PW_WAVE_LOOP(kLoader ? pw_load_step(p, sh, ring) : pw_step(p, sh, zero_row, ring));
     return ok;
 }
 ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t wave, const ChainDesc &c, int planes, int sign_bit, uint16_t *plane, size_t stride,
@@ -598,24 +593,7 @@ ICER_DEV bool pw_run_chain(uint8_t *lds, uint32_t wave, const ChainDesc &c, int 
     if (wave >= nrun) return true;
     PlaneWave p;
     pw_init(p, wave, nrun, c, planes, sign_bit, plane, stride, stream, stream_len, t);
-    // (pw_wave_loop<false>, kept in its own words: routed through the template, the register figures of the kernels that call
-    // this function move, and they are pinned -- profiles/decode_session.md)
-    bool ok = true;
-    while (p.r < p.h) {
-        uint32_t need;
-        const uint32_t *word = pw_wait_for(p, sh, &need);
-        uint32_t spins = 0;
-        while (PW_UNIFORM(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) < need) {
-            if (spins < 6u) __builtin_amdgcn_s_sleep(2);
-            else if (spins < 12u) __builtin_amdgcn_s_sleep(16);
-            else __builtin_amdgcn_s_sleep(127);
-            spins++;
-            if (spins > kPwSpinLimit || ((spins & 63u) == 0u && PW_UNIFORM(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0u)) { ok = false; break; }
-        }
-        if (!ok) break;
-        if (pw_step(p, sh, zero_row, ring) == 0) { ok = false; break; }     // (cannot be: the condition just held and only grows)
-    }
-    if (!ok && (threadIdx.x & 63u) == 0u) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    PW_WAVE_LOOP(pw_step(p, sh, zero_row, ring));                // (not pw_wave_loop<false>: see there)
     return ok;
 }
 // the same for a chain of a decode session (pw_resume_shape): wave 0 loads when planes are held, and like every wave it

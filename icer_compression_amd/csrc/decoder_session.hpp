@@ -37,7 +37,7 @@ decode_chains_resume_kernel(uint16_t *state, size_t frame_stride, int channels, 
     const FrameInfo f = frames[c.frame];
     PlaneDecoder job;
     plane_attach_columns(job, lds_state, 64u, threadIdx.x);
-    decode_chain_resume(job, state + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband, data + f.stream_off,
+    decode_chain_resume(job, chain_plane(state, c, channels, frame_stride), f.w, c, (int)c.subband, data + f.stream_off,
                         f.stream_len, lt, nplanes, sign_bit, lowest_ok + i);
 }
 
@@ -51,18 +51,9 @@ decode_chains_planes_resume_kernel(uint16_t *state, size_t frame_stride, int cha
     ICER_DYNAMIC_LDS(uint8_t, lds);
     const ChainDesc &c = chains[blockIdx.x];                  // (read in place: see pw_run_chain)
     const FrameInfo f = frames[c.frame];
-#ifndef ICER_HOST_MOCK
-    {   // control words, zero row and ring start out zero
-        uint32_t *w = reinterpret_cast<uint32_t *>(lds);
-        const uint32_t words = (uint32_t)((pw_lds_bytes(c.w, nplanes) + 3u) / 4u);
-        for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) w[i] = 0;
-        __syncthreads();
-    }
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
-    const uint32_t wave = 0;
-#endif
-    (void)pw_run_chain_resume(lds, wave, c, nplanes, sign_bit, state + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w,
+    pw_workgroup_clear(lds, c, nplanes);
+    const uint32_t wave = pw_workgroup_wave();
+    (void)pw_run_chain_resume(lds, wave, c, nplanes, sign_bit, chain_plane(state, c, channels, frame_stride), f.w,
                               data + f.stream_off, f.stream_len, tables, err);
 }
 
@@ -78,7 +69,7 @@ decode_chains_wave_resume_kernel(uint16_t *state, size_t frame_stride, int chann
     const ChainDesc c = chains[blockIdx.x];
     const FrameInfo f = frames[c.frame];
     uint16_t *ring = reinterpret_cast<uint16_t *>(lds + kStateBytes);
-    decode_chain_wave_resume(ring, state + ((size_t)c.frame * channels + c.chan) * frame_stride, f.w, c, (int)c.subband, data + f.stream_off,
+    decode_chain_wave_resume(ring, chain_plane(state, c, channels, frame_stride), f.w, c, (int)c.subband, data + f.stream_off,
                              f.stream_len, lt, nplanes, sign_bit, nullptr, lds, lowest_ok + blockIdx.x);
 }
 

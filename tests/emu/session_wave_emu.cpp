@@ -6,7 +6,9 @@
 // A case file holds streams and the images the decoder oracle makes of them (tests/test_session_wave_emu.py writes it).  Every
 // chain of every stream is decoded in two goes, split at every plane boundary: the top s planes by decode_chain_wave, the rest by
 // decode_chain_wave_resume in place on the same plane, its ring and per-lane state in heap blocks of exactly the size the kernel
-// reserves.  s = 0 is the resume function on an empty plane: it must do what the plain one does.  Per resumed chain the program checks
+// reserves.  s = 0 is the resume function on an empty plane: it must do what the plain one does -- the two are instantiations of one
+// body, and the program runs decode_chain_wave on a copy of the plane and requires the same words and the same schedule counts
+// (iterations, samples, roll-backs, rows not retired).  Per resumed chain the program checks
 //   - *lowest_ok against decode_chain_resume (decoder_core.hpp) run on a copy of the plane as it was before;
 //   - that no bit of a held plane, and no sign of a sample those planes made significant, has changed;
 //   - for the packet a case names as failing: that lowest_ok is the plane above it.  (A chain whose failing plane lies in the top
@@ -24,8 +26,8 @@ using namespace icer;
 
 // decode_chain_wave_resume's own counts ([2] roll-backs, [3] chains that ended with rows not retired, [4] rows reloaded from the state
 // plane), and the program's: calls with held planes, calls with none, chains that reported a stop, of them below a held plane,
-// roll-backs below a held plane
-static unsigned long long g_wave[5], g_resumes, g_fresh, g_stops, g_stops_below_held, g_rollbacks_below_held;
+// roll-backs below a held plane, calls with no plane held that were repeated by decode_chain_wave and compared
+static unsigned long long g_wave[5], g_resumes, g_fresh, g_stops, g_stops_below_held, g_rollbacks_below_held, g_plain_checked;
 
 static bool fail(const char *what, const ChainDesc &c, int held)
 {
@@ -45,7 +47,7 @@ static bool run_resume(uint16_t *plane, size_t stride, size_t words, const Chain
     PlaneStorage own;
     plane_attach_local(job, own);
     uint32_t want_ok = 0, ok = 0xFFFFFFFFu;
-    const unsigned long long rollbacks = g_wave[2];
+    const unsigned long long rollbacks = g_wave[2], wave_before[4] = {g_wave[0], g_wave[1], g_wave[2], g_wave[3]};
     decode_chain_resume(job, copy.data(), stride, c, (int)c.subband, stream, stream_len, t, planes, sign_bit, &want_ok);
     std::vector<uint16_t> ring(ring_elems_for(c.w, planes), (uint16_t)0xA5A5u);       // (the function fills its ring itself)
     std::vector<uint8_t> state(kStateBytes, 0);
@@ -54,6 +56,19 @@ static bool run_resume(uint16_t *plane, size_t stride, size_t words, const Chain
     if (held) g_rollbacks_below_held += g_wave[2] - rollbacks;
     if (ok != want_ok) return fail("lowest_ok differs from decode_chain_resume's", c, held);
     if (memcmp(plane, copy.data(), sizeof(uint16_t) * words) != 0) return fail("the plane differs from decode_chain_resume's", c, held);
+    if (held == 0) {
+        // nothing held: the two instantiations of the one body are one schedule -- the same words, iteration for iteration
+        std::vector<uint16_t> plain(before), plain_ring(ring_elems_for(c.w, planes), (uint16_t)0xA5A5u);
+        std::vector<uint8_t> plain_state(kStateBytes, 0);
+        unsigned long long plain_stats[5] = {0, 0, 0, 0, 0};
+        decode_chain_wave(plain_ring.data(), plain.data(), stride, c, (int)c.subband, stream, stream_len, t, planes, sign_bit, plain_stats,
+                          plain_state.data());
+        if (memcmp(plane, plain.data(), sizeof(uint16_t) * words) != 0) return fail("the plane differs from decode_chain_wave's", c, held);
+        for (int k = 0; k < 4; k++)
+            if (g_wave[k] - wave_before[k] != plain_stats[k]) return fail("the schedule's counts differ from decode_chain_wave's", c, held);
+        if (plain_stats[4] != 0) return fail("decode_chain_wave counted a reload", c, held);
+        g_plain_checked++;
+    }
     const uint32_t held_mask = ((1u << sign_bit) - 1u) & ~((1u << (planes - held)) - 1u), sign = 1u << sign_bit;
     for (size_t i = 0; held && i < words; i++) {
         const uint32_t a = before[i], b = plane[i];
@@ -171,7 +186,8 @@ int main(int argc, char **argv)
         cases++;
     }
     fclose(f);
-    printf("cases %llu runs %llu resumes %llu fresh_runs %llu reloaded_rows %llu rollbacks %llu rollbacks_below_held %llu stops %llu stops_below_held %llu\n",
-           cases, runs, g_resumes, g_fresh, g_wave[4], g_wave[2], g_rollbacks_below_held, g_stops, g_stops_below_held);
+    printf("cases %llu runs %llu resumes %llu fresh_runs %llu reloaded_rows %llu rollbacks %llu rollbacks_below_held %llu stops %llu stops_below_held %llu "
+           "plain_checked %llu\n",
+           cases, runs, g_resumes, g_fresh, g_wave[4], g_wave[2], g_rollbacks_below_held, g_stops, g_stops_below_held, g_plain_checked);
     return 0;
 }

@@ -70,6 +70,8 @@ def test_every_shape_split_at_every_plane(program, tmp_path, oracle):
     stats = run(program, tmp_path, cases)
     assert stats["cases"] == len(cases) and stats["runs"] == stats["cases"] * 10
     assert stats["resumes"] > 0 and stats["fresh_runs"] > 0, stats
+    # (every call with no plane held was repeated by decode_chain_wave: the same words, the same schedule counts)
+    assert stats["plain_checked"] == stats["fresh_runs"], stats
     assert stats["reloaded_rows"] > 0, "no recycled ring slot ever took a row of the state plane"
     assert stats["rollbacks"] == 0 and stats["stops"] == 0, stats
 
