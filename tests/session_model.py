@@ -9,13 +9,16 @@ slot nothing).  A feed with a packet of another size than the slot's (not yet kn
 LL mean than the slot's for that channel, is refused: INVALID_INPUT, slot untouched, nothing delivered; an image of more than
 frame_stride samples likewise, with QUOTA.  Per chain the feed contributes the planes next, next - 1, ...
 for as long as it has them, next being one below the chain's lowest held plane (the top plane for a chain that holds none);
-everything else is dropped and counted.  What the session delivers is the plain decode of the packets of T as one stream
-(the oracle; reduced_model / recon_model for a reduced decoder and for a reconstruction setting).
+everything else is dropped and counted.  stats()[2] is "planes decoded": of the accepted planes those whose chain the plan of
+the slot's image runs (`planned`) -- all of them, unless a subband's segment grid fails (quirk P1), where the plan stops and the
+chains at and behind the stop are held but never run.  What the session delivers is the plain decode of the packets of T as one
+stream (the oracle; reduced_model / recon_model for a reduced decoder and for a reconstruction setting).
 
 Not modelled: a chain that stops for good at a plane whose entropy decode fails (the oracle does not say which plane of which
 chain failed); the tests feed no such packet."""
 from tests import recon_model as rcm
 from tests import reduced_model as red
+from tests import target_model as tm
 
 OK, QUOTA, INVALID_INPUT = 0, -5, -11
 MAX_STAGES, MAX_SEGMENTS, MAX_PLANES = 6, 32, 9
@@ -23,7 +26,7 @@ MAX_STAGES, MAX_SEGMENTS, MAX_PLANES = 6, 32, 9
 
 class Slot:
     def __init__(self):
-        self.T, self.size, self.mean = {}, None, {}
+        self.T, self.size, self.mean, self.low = {}, None, {}, {}             # low: per chain the lowest plane in T
 
 
 class SessionModel:
@@ -32,7 +35,8 @@ class SessionModel:
         self.frame_stride, self.bits, self.r, self.k = frame_stride, bits, reduce, reconstruct
         self.planes = 9 if bits == 16 else 7
         self.slots = [Slot() for _ in range(n_slots)]
-        self.decoded = self.dropped = 0               # planes accepted, packets dropped: stats()[2], stats()[3]
+        # planes decoded, packets dropped: stats()[2], stats()[3]; runs: (feed, chain) pairs that brought a chain new planes to decode
+        self.decoded = self.dropped = self.runs = 0
 
     def reset(self, slot=-1):
         for k in range(len(self.slots)) if slot < 0 else [slot]:
@@ -40,11 +44,29 @@ class SessionModel:
 
     def lowest(self, slot, chain):
         """the lowest plane the chain (channel, level, subband, segment) holds; self.planes: none"""
-        held = [key[4] for key in self.slots[slot].T if key[:4] == chain]
-        return min(held) if held else self.planes
+        return self.slots[slot].low.get(chain, self.planes)
 
     def planes_held(self, slot, ch, lv, sb, sg):
         return self.planes - self.lowest(slot, (ch, lv, sb, sg))
+
+    def planned(self, key, w, h):
+        """does the plan of a w x h image (csrc/decoder_plan.hpp plan_chains) run the chain of packet `key`?  The plan visits
+        level 1 .. stages - r, in it the channels, in them LL (deepest level only), HL, LH, HH, and stops for good at the first
+        subband whose segment grid fails (quirk P1: rc -3, what was decoded before stays).  A packet of a chain at or behind
+        the stop, or of a chain the plan does not have, is accepted and held like any other -- planes_held counts it -- but
+        is never decoded and never shows in an image."""
+        ch, lv, sb, sg = key[0], key[1] - self.r, key[2], key[3]
+        S = self.stages - self.r
+        if not (1 <= lv <= S and ch < self.channels and sg < self.segments and (sb > 0 or lv == S)):
+            return False
+        for l in range(1, lv + 1):
+            for c in range(self.channels):
+                for s in range(0 if l == S else 1, 4):
+                    if tm.grid_fails(*tm.subband_rect(w, h, l, s)[:2], self.segments):
+                        return False
+                    if (l, c, s) == (lv, ch, sb):
+                        return True
+        return False
 
     def stream_of(self, slot):
         """the packets of T as one stream (a decoder does not mind their order)"""
@@ -91,7 +113,11 @@ class SessionModel:
             sl.size = size
             sl.mean.update({ch: mean[ch] for ch in {key[0] for key in took}})
         sl.T.update(took)
-        accepted = len(took)
-        self.decoded += accepted
-        self.dropped += walked - accepted
+        for key in took:
+            sl.low[key[:4]] = min(sl.low.get(key[:4], self.planes), key[4])
+        # an accepted packet is not dropped; it counts as decoded where the plan runs its chain (`planned`)
+        ran = [key for key in took if self.planned(key, w, h)]
+        self.decoded += len(ran)
+        self.runs += len({key[:4] for key in ran})
+        self.dropped += walked - len(took)
         return self.decode(slot, w0, h0)
